@@ -1,7 +1,14 @@
 """RAFT 12-iteration inference throughput on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sintel|kitti|corr]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sintel|kitti|corr] [--dump-outputs DIR] [--full]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write the last timed step's
+outputs if ``--dump-outputs DIR`` is given (DIR/<name>.npy, float32: what a caller of the timed path receives; the
+inputs are the same from run to run, so two builds can be compared output for output) and print the result line
+(metric / value / unit / higher_is_better / dtype / ms_per_step and the configuration). Everything else described
+below -- the per-kernel events and rooflines, ``roofline.step``'s extra forward, the API lookup and warp legs,
+``epe_vs_reference`` and the CPU baseline -- runs only with ``--full``.
 
 Both forms run N ranks. Under torchrun (WORLD_SIZE set) this process is one rank. Without WORLD_SIZE and with
 --gpus N > 1, this process is only a launcher (``launch_ranks``): before any GPU call it starts N fresh rank processes
@@ -18,8 +25,8 @@ dataset or checkpoint is reachable offline.
 Inputs: the 8 pairs of the reference-generated golden batch (tests/golden/raft_e2e_batch.npz: 'sintel8' / 'kitti8',
 synthetic frames the repository's generator rebuilds bit for bit), tiled to the global batch.
 
-Printed (rank 0, one JSON line): pairs/s for the whole job, the lookup kernel's roofline (algorithmic bytes per
-launch / mean launch time from HIP events recorded on the launch stream inside the timed region), ``roofline.step``
+Printed (rank 0, one JSON line): pairs/s for the whole job, and with ``--full`` the lookup kernel's roofline
+(algorithmic bytes per launch / mean launch time from HIP events recorded on the launch stream inside the timed region), ``roofline.step``
 (the whole step's executed f16 MFMA rate against the dense peak, counted per launch in one extra untimed forward),
 the corr pyramid kernel's MFMA rate, ``epe_vs_reference`` (the LAST TIMED STEP's flows for the golden batch's pairs
 against the reference's own flows for them), and the oracle (PyTorch-CPU restatement) timed on this host's cores on
@@ -370,6 +377,31 @@ def golden_epe(model, dev, workload: str):
     }
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs writes at most this much in all (under 64 MB)
+DUMP_SEED = 0
+
+
+def dump_outputs(dirname: str, arrays) -> dict:
+    """``--dump-outputs``: write ``arrays`` ({name: tensor}, the last timed step's outputs) as float32 DIR/<name>.npy.
+    When they exceed DUMP_BUDGET_BYTES together, every array is cut to the same fraction of its elements: a fixed
+    sample of its flattened values at sorted indices drawn (with replacement) from numpy's default_rng(DUMP_SEED), so
+    two runs with the same arguments write the same elements. Returns {name: {shape, written}} for the result line."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: v.detach().to(torch.float32).cpu().contiguous().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    keep = min(1.0, DUMP_BUDGET_BYTES / max(1, total))
+    info = {}
+    for k, (name, a) in enumerate(host.items()):
+        if keep < 1.0:
+            idx = np.sort(np.random.default_rng(DUMP_SEED + k).integers(0, a.size, size=max(1, int(a.size * keep))))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        info[name] = {"shape": list(host[name].shape), "written": int(a.size)}
+    return info
+
+
 def _free_port() -> int:
     import socket
 
@@ -472,9 +504,16 @@ def main() -> int:
     ap.add_argument("--workload", default="sintel", choices=sorted(WORKLOADS))
     ap.add_argument("--pairs-per-gpu", type=int, default=None)
     ap.add_argument("--iters", type=int, default=None, help="GRU iterations (default: the workload's 12)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-events", action="store_true", help="do not record per-kernel HIP events")
-    ap.add_argument("--conv-events", action="store_true", help="also time every update-block conv launch")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: per-kernel HIP events and "
+                         "rooflines, the step's flop count (one more forward), the API lookup and warp legs, the EPE "
+                         "against the reference's golden flows, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (float32, at "
+                         "most 64 MB in all: a fixed seeded sample of larger outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-events", action="store_true", help="--full: do not record per-kernel HIP events")
+    ap.add_argument("--conv-events", action="store_true", help="--full: also time every update-block conv launch")
     ap.add_argument("--update-impl", default="split", choices=["split", "fused", "module"])
     ap.add_argument("--graph", action="store_true",
                     help="replay each rank's forward from a HIP graph (model/graph.py: one launch per step); the default "
@@ -487,7 +526,8 @@ def main() -> int:
                     help="steps in flight: step i is issued on stream i %% N (its own side streams), so step i+1's "
                          "encoders run beside step i's update loop (pairs are independent; every step's flows are its own)")
     ap.add_argument("--no-step-flops", action="store_true",
-                    help="skip the untimed flop-counting forward (roofline.step), e.g. under a kernel-trace profiler")
+                    help="--full: skip the untimed flop-counting forward (roofline.step), e.g. under a kernel-trace "
+                         "profiler")
     ap.add_argument("--no-comm-overlap", action="store_true",
                     help="N > 1: run scatter -> forward -> gathers back to back per step (default: the scatter of step "
                          "i+1 and the gathers of step i overlap step i's / i+1's forward, model/pair_sharding.py "
@@ -505,6 +545,13 @@ def main() -> int:
     if args.graph and args.eager:
         print("bench: --graph and --eager exclude each other", file=sys.stderr)
         return 2
+    if args.conv_events and not args.full:
+        print("bench: --conv-events needs --full", file=sys.stderr)
+        return 2
+    # a plain run times the steps and nothing else: what --full adds beside the headline figure
+    events = args.full and not args.no_events
+    count_flops = args.full and not args.no_step_flops
+    cpu_base = args.full and not args.no_cpu_baseline
     # graph replay by default for the RAFT workloads (one capture per rank; with --graph --inflight N, N captures,
     # step i replaying capture i %% N on stream i %% N: each capture owns its static buffers)
     args.graph = args.graph or (not args.eager and args.workload in ("sintel", "kitti") and args.inflight == 1
@@ -576,7 +623,8 @@ def main() -> int:
     padder = InputPadder((h, w), mode=pmode or "sintel")
     dims = _native.pyramid_dims((h + 7) // 8, (w + 7) // 8, 4)
     # without a batch golden for this workload: the 1-pair golden through the benchmarked model, before timing
-    epe = golden_epe(model, dev, args.workload) if args.workload != "corr" and rank == 0 and not gtag else None
+    epe = (golden_epe(model, dev, args.workload)
+           if args.full and args.workload != "corr" and rank == 0 and not gtag else None)
     shard_shape = (global_batch, 3, h, w)
     flow_shapes = ((2, dims[0][0], dims[0][1]), (2, h, w))
 
@@ -594,7 +642,7 @@ def main() -> int:
         pp = padder.pad(*(torch.zeros((ppg, 3, h, w), device=dev),) * 2)
         # per-kernel timing inside the graph: native event-record nodes captured around the timed launches, re-recorded
         # by every replay (read after the timed region: they time its last replay)
-        graph_rec = None if args.no_events else ({"_native": True, "*": True} if args.conv_events else {"_native": True})
+        graph_rec = None if not events else ({"_native": True, "*": True} if args.conv_events else {"_native": True})
         # one capture per step in flight (the first holds the timing nodes); fwd() replays them in turn, and issue(i)
         # runs step i on stream i % inflight, so consecutive replays of one capture stay ordered on one stream
         ngraphs = max(1, args.inflight) if world == 1 else 1
@@ -645,7 +693,7 @@ def main() -> int:
         run_steps(nwarm)
         torch.cuda.synchronize(dev)
         # graph replays launch no Python: their per-kernel events are the graph's own nodes (graph_rec, captured above)
-        rec = ({"*": True} if args.conv_events else {}) if not (args.no_events or args.graph) else None
+        rec = ({"*": True} if args.conv_events else {}) if events and not args.graph else None
         _native.set_event_recorder(rec)
         if world > 1:
             dist.barrier()
@@ -662,11 +710,16 @@ def main() -> int:
             rec, rec_forwards = graph_rec, 1  # the last replay's launches
         if getattr(model, "range_guard", "off") == "deferred":
             model.check_range(dev)  # every timed forward's split operands were in range (raises otherwise)
-        if rank == 0 and gtag:
+        dumped = None
+        if rank == 0 and args.dump_outputs:
+            # before anything else runs: a graph replay's outputs are the capture's buffers
+            dumped = dump_outputs(args.dump_outputs, {"corr_lookup": out[0]} if args.workload == "corr"
+                                  else {"flow_low": out[0], "flow_up": out[1]})
+        if rank == 0 and gtag and args.full:
             epe = step_epe(out, gtag, gfix, global_batch)
         # one more (untimed) forward with the per-launch flop counter: the step roofline
         step_flops = None
-        if args.workload != "corr" and not args.no_step_flops:
+        if args.workload != "corr" and count_flops:
             cnt = {}
             _native.set_flop_counter(cnt)
             forward(img0[:ppg] if img0 is not None else torch.zeros((ppg, 3, h, w), device=dev),
@@ -726,6 +779,7 @@ def main() -> int:
             "update_impl": args.update_impl,
             "hip_graph": bool(args.graph),
             "steps_in_flight": max(1, args.inflight),
+            "full": bool(args.full),
         },
     }
     if rec and args.conv_events:
@@ -830,7 +884,9 @@ def main() -> int:
         line.setdefault("roofline", {})["step"] = step
     if epe is not None:
         line["epe_vs_reference"] = {k: (round(v, 8) if isinstance(v, float) else v) for k, v in epe.items()}
-    if rank == 0 and not args.no_cpu_baseline and args.workload in ("sintel", "kitti"):
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if rank == 0 and cpu_base and args.workload in ("sintel", "kitti"):
         # after every rank's timing (the all-reduce above): the oracle on rank 0's host cores, a bounded sample
         line["cpu_baseline"] = cpu_baseline(h, w, iters, ppg)
     if rank == 0:

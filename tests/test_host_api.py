@@ -143,6 +143,35 @@ def test_bench_batch_golden_and_step_epe(golden):
     assert bench.batch_golden("hd", 1080, 1920, 24) == (None, None)
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (host logic): float32 <name>.npy of each output, whole when they fit the budget; past
+    it the same fixed sample of every array in two calls, and no more bytes than the budget in all."""
+    import numpy as np
+
+    import bench
+
+    low = torch.arange(2 * 2 * 5 * 7, dtype=torch.float64).reshape(2, 2, 5, 7)
+    up = torch.arange(2 * 2 * 40 * 56, dtype=torch.float32).reshape(2, 2, 40, 56) * 0.5
+    info = bench.dump_outputs(str(tmp_path / "a"), {"flow_low": low, "flow_up": up})
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("flow_low", "flow_up")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["flow_low"], low.numpy()) and np.array_equal(got["flow_up"], up.numpy())
+    assert info["flow_up"] == {"shape": [2, 2, 40, 56], "written": up.numel()}
+
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 1000 * 1000
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 1000)
+    bench.dump_outputs(str(tmp_path / "b"), {"flow_low": low, "flow_up": up})
+    bench.dump_outputs(str(tmp_path / "c"), {"flow_low": low, "flow_up": up})
+    total = 0
+    for n, full in (("flow_low", low), ("flow_up", up)):
+        b, c = np.load(tmp_path / "b" / (n + ".npy")), np.load(tmp_path / "c" / (n + ".npy"))
+        assert b.dtype == np.float32 and b.ndim == 1 and 0 < b.size < full.numel()
+        assert np.array_equal(b, c)
+        assert np.isin(b, full.numpy().astype(np.float32)).all()
+        total += b.nbytes
+    assert total <= 4 * 1000
+
+
 def test_cached_pack_keys_and_rebuilds():
     """The packed-weight cache (model.update.cached_pack): a hit returns the cached object, a new key rebuilds; on a
     CPU-only host no event is recorded."""

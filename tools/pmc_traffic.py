@@ -1,8 +1,8 @@
 """Per-launch HBM traffic of the corr_lookup kernel from rocprofv3 PMC passes -> profiles/lookup_traffic.json.
 
 Counters are collected in separate passes of the same bench command (MI355X_MICROARCH.md §HBM / rocprofv3 PMC):
-    rocprofv3 --pmc TCC_EA0_RDREQ_sum --kernel-include-regex corr_lookup ... -- python bench.py ...
-    rocprofv3 --pmc WRITE_SIZE        --kernel-include-regex corr_lookup ... -- python bench.py ...
+    rocprofv3 --pmc TCC_EA0_RDREQ_sum --kernel-include-regex corr_lookup ... -- python bench.py --full ...
+    rocprofv3 --pmc WRITE_SIZE        --kernel-include-regex corr_lookup ... -- python bench.py --full ...
 Corrections (gfx950):
   * reads: FETCH_SIZE = TCC_EA0_RDREQ x 64 B, but the guide notes that wide reads issue 128-B requests tallied at
     64 B. Calibrated on this kernel's own pattern: the canonical-layout lookup issues 1.81 M requests per Sintel x8

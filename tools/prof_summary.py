@@ -37,7 +37,8 @@ def main():
     ap.add_argument("path")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--skip-last", type=int, default=0,
-                    help="anchors after the timed region to ignore (bench.py's API lookup leg builds 2 pyramids)")
+                    help="anchors after the timed region to ignore (bench.py --full's API lookup leg builds 2 "
+                         "pyramids)")
     ap.add_argument("--anchor", default="corr_pyramid")
     ap.add_argument("--top", type=int, default=40)
     a = ap.parse_args()
