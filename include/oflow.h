@@ -57,6 +57,8 @@ extern "C" {
 #define OFLOW_IN_F32 2
 #define OFLOW_IN_IMG7S2 3
 #define OFLOW_IN_FLOW7 4
+/* oflow_conv_s32_ex6: the flow-head epilogue (epilogues 0-2: oflow_conv_s32) */
+#define OFLOW_EPI_FLOW_HEAD 3
 
 int oflow_abi_version(void);
 const char* oflow_status_string(int status);
@@ -202,6 +204,18 @@ int oflow_flow_prep_s32(const float* d_coords, int B, int H, int W, void* d_patc
  * delta_flow) as a 1x1 conv C -> 18 per-tap products (oflow_conv_s32 with an fp32 NCHW destination d_y (B, 18, H, W))
  * followed by this gather. */
 int oflow_flow_head_col2im_f32(const float* d_y, const float* d_bias, int B, int H, int W, float* d_coords, void* stream);
+/* oflow_flow_head_finish_f32: the second half of the flow head folded into conv1 (oflow_conv_s32_ex6,
+ * OFLOW_EPI_FLOW_HEAD) and the next iteration's flow channels. Per pixel and output channel c, in this order:
+ *   s = 0; for t = 0..8 (ky = t / 3, kx = t % 3), for slab = 0..slabs-1:
+ *     s += d_partial[slab][b][t*2 + c][y + ky - 1][x + kx - 1]   (neighbours outside the image contribute nothing);
+ *   d_coords[b][c][y][x] += s + d_bias[c]      (raft.py:133 coords1 = coords1 + delta_flow; d_coords contiguous)
+ * then flow = coords1 - coords0 of the UPDATED coords1 (raft.py:129; coords0 the pixel grid) goes, split into fp16
+ * hi + lo, into the two flow channels of the GRU input buffers d_flow0 / d_flow1 (NULL: not written) -- the bytes, and
+ * the range-flag behaviour, of oflow_flow_prep_s32 called on the updated coords1 with the same destinations.
+ * d_partial: [slabs][B][18][H][W] fp32, slabs = 4. */
+int oflow_flow_head_finish_f32(const float* d_partial, int slabs, const float* d_bias, int B, int H, int W,
+                               float* d_coords, void* d_flow0, long long flow0_pixel_stride, void* d_flow1,
+                               long long flow1_pixel_stride, void* stream);
 
 /* oflow_normalize_images_f32: y = 2 * (x / 255) - 1 for two frames of n fp32 values each (4-B aligned; vector loads
  * when n % 4 == 0 and 16-B aligned): RAFT.forward's input scaling (methods/raft/model/raft.py:104-105), the reference's
@@ -371,6 +385,30 @@ int oflow_conv_s32_ex5(const void* d_x, long long x_pixel_stride, int in_groups,
                        const float* d_in_scale, const float* d_in_shift, const float* d_addend,
                        long long addend_pixel_stride, const void* d_wfrag, float* d_ksplit_slab,
                        unsigned* d_ksplit_ctr, long long ksplit_tiles, void* stream);
+/* oflow_conv_s32_ex6: oflow_conv_s32_ex5 plus epilogue OFLOW_EPI_FLOW_HEAD: the flow head (update.py:31-37,
+ * conv2(relu(conv1(x)))) with its 256 -> 2 output conv folded into conv1's epilogue. The call is conv1 (3x3, S32 input,
+ * N = n_pad = 256, activation 1 = ReLU, out_scale 1, block_n 64 or 128; 128 needs d_wfrag); relu(conv1) is never
+ * stored. Per pixel and 64-channel slab the epilogue forms the 18 per-tap products of conv2 at that INPUT pixel,
+ *   d_fh_partial[slab][b][t*2 + c][y][x] = sum_{ch in slab} relu(conv1)[b][slab*64 + ch][y][x] * W2[c][slab*64 + ch][ky][kx],
+ *   t = ky*3 + kx   (fp32, [fh_slabs][B][18][H][W], every in-image element written on every call),
+ * as fp32 FMAs on the fp32 values (nothing is re-split to fp16) in an order that depends on the channel's index within
+ * the slab only -- two fmaf chains over the slab's even and odd channels, each ascending, then even + odd -- so every
+ * block_n and weight staging gives the same bits. oflow_flow_head_finish_f32 gathers the taps and slabs.
+ *   d_fh_weights: conv2's weight (2, 256, 3, 3) repacked [slab 4][channel 64][t*2 + c] fp32;
+ *   fh_slabs: N / 64 = 4 (else OFLOW_E_SHAPE). Every destination of the other epilogues, d_addend and the split-K
+ *   buffers must be NULL (OFLOW_E_MODE). Always the default 4 x 32 tiles, small grids included.
+ * Any other epilogue: oflow_conv_s32_ex5 (the three flow-head arguments ignored). */
+int oflow_conv_s32_ex6(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack, int n_pad,
+                       const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh, int kw,
+                       int block_n, int epilogue, int activation, float out_scale, void* d_y0, long long y0_pixel_stride,
+                       void* d_y1, long long y1_pixel_stride, float* d_f32, long long f32_batch_stride,
+                       long long f32_channel_stride, int f32_accumulate, float* d_gru_h, float* d_gru_z,
+                       int gru_channels, float* d_nhwc, int nhwc_pixel_stride, float* d_stats, const void* d_res,
+                       long long res_pixel_stride, int res_activation, int s2d, int in_format,
+                       const float* d_in_scale, const float* d_in_shift, const float* d_addend,
+                       long long addend_pixel_stride, const void* d_wfrag, float* d_ksplit_slab,
+                       unsigned* d_ksplit_ctr, long long ksplit_tiles, const float* d_fh_weights, float* d_fh_partial,
+                       int fh_slabs, void* stream);
 int oflow_stem_patches_s32(const float* d_img, int B, int C, int H, int W, void* d_out, int out_groups, void* stream);
 int oflow_norm_stats_finalize(const float* d_partials, int B, int tiles, int n_pad, int C, double eps, float* d_alpha,
                               float* d_beta, void* stream);

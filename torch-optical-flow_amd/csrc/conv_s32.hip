@@ -125,7 +125,12 @@ struct ConvArgs {
   float* ks_slab;
   unsigned* ks_ctr;
   long long ks_tiles;      // tiles (x channel blocks) the slab and counters hold
+  // flow-head epilogue (EPI 3, oflow_conv_s32_ex6): the output conv's weights [slab][64][18] and the per-tap partial
+  // sums [slabs][B][18][H][W] (fp32)
+  const float* fhw;
+  float* fhy;
 };
+constexpr int kEpiFlowHead = OFLOW_EPI_FLOW_HEAD;
 // input formats of oflow_conv_s32_ex2
 constexpr int kInS32 = OFLOW_IN_S32, kInF32Norm = OFLOW_IN_F32_NORM, kInF32 = OFLOW_IN_F32, kInImg = OFLOW_IN_IMG7S2,
               kInFlow = OFLOW_IN_FLOW7;
@@ -180,6 +185,73 @@ __device__ __forceinline__ void store_s32(uint8_t* y, long long ps, long long P,
         lp[j] = l_;
       }
     }
+  }
+}
+
+// Flow-head epilogue (EPI 3; update.py:35-36 FlowHead: conv2(relu(conv1(x))), conv2 3x3 256 -> 2). The tile holds
+// relu(conv1) of 128 pixels x BN channels in fp32; instead of storing it, the workgroup forms, per pixel and per
+// 64-channel slab of its block, the 18 per-tap products of conv2 at that INPUT pixel,
+//   Y[slab][b][t*2 + c][y][x] = sum_{ch in slab} tile[p][ch] * W2[c][ch][ky][kx],  t = ky*3 + kx,
+// which oflow_flow_head_finish_f32 gathers over the 3x3 neighbourhood and the slabs. One lane = one pixel (a wave = two
+// 32-pixel tile rows: each Y store of a wave is two whole 128-B lines), one wave = one slab and taps [T0, T1); the
+// weights are wave-uniform ([slab][channel][18] fp32, read through the scalar cache into SGPRs: no LDS or vector-memory
+// traffic), the tile values one conflict-free 8-B LDS read per two channels.
+// Summation order (a fixed function of the channel index within the slab, whatever the block size, the wave grid or
+// the weight staging): two fmaf chains per output, over the slab's even and its odd channels, each ascending from 0.f;
+// Y = even + odd. fp32 FMAs on the fp32 tile values: nothing is split to fp16, so there is no range guard here.
+typedef __attribute__((address_space(4))) const float cfloat;  // constant address space: uniform reads become s_load
+template <int T0, int T1>
+__device__ __forceinline__ void flow_head_partials(const float* tp, cfloat* w, float* yp, long long plane, bool in) {
+  constexpr int NO = 2 * (T1 - T0);
+  float acc[2][NO];
+#pragma unroll
+  for (int j = 0; j < NO; ++j) acc[0][j] = acc[1][j] = 0.f;
+  // the next channel pair's weights and tile values are requested before this pair's FMAs and waited for after them
+  // (a scalar-cache and an LDS round trip per step otherwise; scalar loads return out of order, so any wait on the
+  // LDS read would wait for the weights too: both are a step ahead)
+  float wn[2][NO];
+#pragma unroll
+  for (int e = 0; e < 2; ++e)
+#pragma unroll
+    for (int j = 0; j < NO; ++j) wn[e][j] = w[e * 18 + 2 * T0 + j];
+  float2 tn = *reinterpret_cast<const float2*>(tp);
+#pragma unroll
+  for (int e = 0; e < 2; ++e)
+#pragma unroll
+    for (int j = 0; j < NO; ++j) asm volatile("" : "+s"(wn[e][j]));  // (complete before the loop: see its end)
+  asm volatile("" : "+v"(tn.x), "+v"(tn.y));
+#pragma unroll 2
+  for (int c0 = 0; c0 < 64; c0 += 2) {
+    float wc[2][NO];
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int j = 0; j < NO; ++j) wc[e][j] = wn[e][j];
+    const float2 t = tn;
+    const int c1 = c0 + 2 < 64 ? c0 + 2 : c0;  // (the last step re-reads its own pair)
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int j = 0; j < NO; ++j) wn[e][j] = w[(c1 + e) * 18 + 2 * T0 + j];
+    tn = *reinterpret_cast<const float2*>(tp + c1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < NO; ++j) {
+      acc[0][j] = fmaf(t.x, wc[0][j], acc[0][j]);
+      acc[1][j] = fmaf(t.y, wc[1][j], acc[1][j]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // (the requested values pinned to registers here, after the FMAs: the compiler otherwise sinks the loads to the
+    // top of the step that uses them and waits for them there)
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int j = 0; j < NO; ++j) asm volatile("" : "+s"(wn[e][j]));
+    asm volatile("" : "+v"(tn.x), "+v"(tn.y));
+  }
+  if (in) {
+#pragma unroll
+    for (int j = 0; j < NO; ++j) yp[(2 * T0 + j) * plane] = acc[0][j] + acc[1][j];
   }
 }
 
@@ -832,11 +904,12 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
   // GRU addend (the hoisted context term): its loads are issued here, so they fly while the accumulators go to LDS,
   // and it is folded into the tile (with the scale and bias) before the GRU state is prefetched -- never both sets
   // of registers live at once
-  const bool has_add = EPI != 0 && a.add != nullptr;
-  u32x4 ad[EPI == 0 ? 1 : KIT][2];
+  constexpr bool GRU = EPI == 1 || EPI == 2;
+  const bool has_add = GRU && a.add != nullptr;
+  u32x4 ad[GRU ? KIT : 1][2];
   if (has_add) {
 #pragma unroll
-    for (int k = 0; k < (EPI == 0 ? 0 : KIT); ++k) {
+    for (int k = 0; k < (GRU ? KIT : 0); ++k) {
       const int item = tid + k * NTH;
       const int pl = item / C8, n = n0 + (item - pl * C8) * 8;
       const int y = ty0 + pl / kTX, x = tx0 + (pl % kTX);
@@ -854,10 +927,22 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
     for (int nt = 0; nt < NT; ++nt) {
       const int nl = wn * (BN / WN) + nt * 32 + r;
       const int pbase = (wm * MT + mt) * kTX;
+      if constexpr (EPI == kEpiFlowHead) {
+        // the tile as relu(scale * acc + bias) (the lane's channel: one (scale, bias) per tile column), the value the
+        // other epilogues form per item (the same fma, ReLU as act_fn's: NaN propagates)
+        const float2 sb = sSB[nl];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int m = (e & 3) + 8 * (e >> 2) + 4 * hh;
+          const float v = fmaf(acc[mt][nt][e], sb.x, sb.y);
+          sT[(pbase + m) * TS + nl] = v < 0.f ? 0.f : v;
+        }
+      } else {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int m = (e & 3) + 8 * (e >> 2) + 4 * hh;
         sT[(pbase + m) * TS + nl] = acc[mt][nt][e];
+      }
       }
     }
   if constexpr (EPI == 0 && TY >= kTY) {
@@ -936,6 +1021,31 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
     }
   }
   __syncthreads();
+  if constexpr (EPI == kEpiFlowHead) {
+    // 4 waves = 2 pixel halves x (BN / 64 slabs x NPART tap ranges): a 64-channel block splits the 9 taps 5 + 4 between
+    // two waves, a 128-channel block gives each wave one slab's 9 taps (see flow_head_partials)
+    constexpr int NSLAB = BN / 64, NPART = NTH / 64 / (2 * NSLAB);
+    static_assert(BM == 128 && BN % 64 == 0 && NTH == 256 && (NPART == 1 || NPART == 2), "flow-head epilogue: 4 x 32 tiles, 4 waves");
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const int sl = (wv >> 1) % NSLAB, part = (wv >> 1) / NSLAB;
+    const int pl = (wv & 1) * 64 + lane;
+    const int y = ty0 + pl / kTX, x = tx0 + (pl % kTX);
+    const bool in = y < a.H && x < a.W;
+    const int slab = (n0 >> 6) + sl;
+    const long long plane = (long long)a.H * a.W;
+    cfloat* w2 = (cfloat*)(a.fhw) + slab * (64 * 18);
+    float* yp = a.fhy + ((long long)slab * a.B + b) * 18 * plane + (long long)y * a.W + x;  // (dereferenced if in)
+    const float* tp = sT + pl * TS + sl * 64;
+    if constexpr (NPART == 1) {
+      flow_head_partials<0, 9>(tp, w2, yp, plane, in);
+    } else {
+      if (part == 0)
+        flow_head_partials<0, 5>(tp, w2, yp, plane, in);
+      else
+        flow_head_partials<5, 9>(tp, w2, yp, plane, in);
+    }
+    return;
+  }
   if (has_add) {
     // pre-activation value = acc * scale + bias + addend, in place (each thread rewrites only its own items, which it
     // alone reads below: no barrier). r05: the item's 8 tile values as two 16-B LDS accesses each way (the main
@@ -949,7 +1059,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
       for (int j = 0; j < 8; ++j) sba[j] = sSB[(tid % C8) * 8 + j];
     }
 #pragma unroll
-    for (int k = 0; k < (EPI == 0 ? 0 : KIT); ++k) {
+    for (int k = 0; k < (GRU ? KIT : 0); ++k) {
       const int item = tid + k * NTH;
       const int pl = item / C8, nl = (item - pl * C8) * 8, n = n0 + nl;
       const int y = ty0 + pl / kTX, x = tx0 + (pl % kTX);
@@ -1304,6 +1414,14 @@ int dispatch_conv(const ConvArgs& a, int kh, int kw, int block_n, int epilogue, 
       if (key == 0x15) return launch_conv<1, 5, 128, 2, 2, 1>(a, s);
       if (key == 0x51) return launch_conv<5, 1, 128, 2, 2, 1>(a, s);
       return OFLOW_E_SHAPE;
+    case kEpiFlowHead:
+      // the flow head's first conv (3x3, S32 input), always on the default 4 x 32 tiles (a lane of a forward computes
+      // what the whole batch computes whatever its own size): LDS-staged 64-channel blocks, or register-direct
+      // 128-channel blocks given the fragment-major weights
+      if (key != 0x33) return OFLOW_E_SHAPE;
+      if (block_n == 64) return launch_conv<3, 3, 64, 2, 2, kEpiFlowHead>(a, s);
+      if (block_n == 128) return a.wf != nullptr ? launch_conv<3, 3, 128, 1, 4, kEpiFlowHead, kTY, true>(a, s) : OFLOW_E_MODE;
+      return OFLOW_E_SHAPE;
     default:
       if (block_n != 128) return OFLOW_E_SHAPE;
       if (small_grid(a, block_n)) {
@@ -1510,6 +1628,49 @@ extern "C" int oflow_conv_s32_ex5(const void* d_x, long long x_pixel_stride, int
       a.wbytes /= 2;
     }
   }
+  return dispatch_conv(a, kh, kw, block_n, epilogue, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int oflow_conv_s32_ex6(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack,
+                                  int n_pad, const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh,
+                                  int kw, int block_n, int epilogue, int activation, float out_scale, void* d_y0,
+                                  long long y0_pixel_stride, void* d_y1, long long y1_pixel_stride, float* d_f32,
+                                  long long f32_batch_stride, long long f32_channel_stride, int f32_accumulate,
+                                  float* d_gru_h, float* d_gru_z, int gru_channels, float* d_nhwc, int nhwc_pixel_stride,
+                                  float* d_stats, const void* d_res, long long res_pixel_stride, int res_activation,
+                                  int s2d, int in_format, const float* d_in_scale, const float* d_in_shift,
+                                  const float* d_addend, long long addend_pixel_stride, const void* d_wfrag,
+                                  float* d_ksplit_slab, unsigned* d_ksplit_ctr, long long ksplit_tiles,
+                                  const float* d_fh_weights, float* d_fh_partial, int fh_slabs, void* stream) {
+  if (epilogue != kEpiFlowHead)
+    return oflow_conv_s32_ex5(d_x, x_pixel_stride, in_groups, d_wpack, n_pad, d_wscale, d_bias, N, B, H, W, kh, kw,
+                              block_n, epilogue, activation, out_scale, d_y0, y0_pixel_stride, d_y1, y1_pixel_stride,
+                              d_f32, f32_batch_stride, f32_channel_stride, f32_accumulate, d_gru_h, d_gru_z,
+                              gru_channels, d_nhwc, nhwc_pixel_stride, d_stats, d_res, res_pixel_stride, res_activation,
+                              s2d, in_format, d_in_scale, d_in_shift, d_addend, addend_pixel_stride, d_wfrag,
+                              d_ksplit_slab, d_ksplit_ctr, ksplit_tiles, stream);
+  // the flow-head epilogue: 3x3 conv 32 * in_groups -> 256 on S32 input, ReLU; its only outputs are the partial sums
+  if (!d_fh_weights || !d_fh_partial) return OFLOW_E_NULL;
+  if (N != 256 || n_pad != 256 || fh_slabs != N / 64 || kh != 3 || kw != 3 || (block_n != 64 && block_n != 128))
+    return OFLOW_E_SHAPE;
+  if (in_format != kInS32 || activation != 1 || out_scale != 1.0f || d_y0 || d_y1 || d_f32 || d_gru_h || d_gru_z ||
+      d_nhwc || d_stats || d_res || s2d || d_addend || d_ksplit_slab || d_ksplit_ctr)
+    return OFLOW_E_MODE;
+  if ((x_pixel_stride & 127) || ((uintptr_t)d_fh_weights & 3) || ((uintptr_t)d_fh_partial & 3)) return OFLOW_E_ALIGN;
+  ConvArgs a;
+  // (the common checks of an epilogue-0 call writing one fp32 destination, which is then dropped)
+  const int st = build_conv_args(a, d_x, x_pixel_stride, in_groups, d_wpack, n_pad, d_wscale, d_bias, N, B, H, W, kh, kw,
+                                 block_n, 0, activation, out_scale, nullptr, 0, nullptr, 0, d_fh_partial, 0, 0, 0, nullptr,
+                                 nullptr, 0, nullptr, 0, nullptr, nullptr, 0, 0, 0);
+  if (st != OFLOW_OK) return st;
+  a.f = nullptr;
+  a.fhw = d_fh_weights;
+  a.fhy = d_fh_partial;
+  if (d_wfrag) {
+    if ((uintptr_t)d_wfrag & 15) return OFLOW_E_ALIGN;
+    a.wf = static_cast<const uint8_t*>(d_wfrag);
+  }
+  a.ain = kInS32;
   return dispatch_conv(a, kh, kw, block_n, epilogue, static_cast<hipStream_t>(stream));
 }
 

@@ -517,6 +517,68 @@ __global__ __launch_bounds__(256) void flow_head_col2im_kernel(const float* __re
   cb[HW] += s[1] + bias[1];
 }
 
+// The flow head folded into its first conv (conv_s32.hip, EPI 3): coords (B, 2, H, W) += bias + the 3x3 gather
+// (flow_head_col2im_kernel's: tap (ky, kx)'s product taken at the neighbour (y + ky - 1, x + kx - 1), zero padding) of
+// the per-tap, per-slab partial sums yp [slabs][B][18][H][W]. Order per output: s = 0; taps ascending, inside a tap the
+// slabs ascending (s += v, or nothing for a neighbour outside the image); then s + bias; then the add into coords.
+// The same thread then writes the next iteration's flow channels of the GRU inputs from the updated coordinates:
+// flow = coords1 - (x, y), the fp32 subtraction, range guard and split of flow_prep_tiled_kernel (the same bytes).
+// One thread per pixel; every plane read is coalesced along x; a thread reads no coordinate but its own pixel's.
+// The kernel closes a lane iteration's serial chain, so it is built for latency: all 72 loads of a thread are issued
+// before the first add (the slab count is a compile-time constant, the loops unrolled), and 64-thread workgroups
+// spread a 4-pair lane's 28160 pixels over 440 workgroups instead of 110.
+constexpr int kFhSlabs = 4, kFhFinishNT = 64;
+__global__ __launch_bounds__(kFhFinishNT) void flow_head_finish_kernel(const float* __restrict__ yp, int B, int H, int W,
+                                                               const float* __restrict__ bias, float* __restrict__ coords,
+                                                               uint8_t* d0, long long d0ps, uint8_t* d1, long long d1ps) {
+  const int HW = H * W;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= B * HW) return;
+  const int b = t / HW, p = t - b * HW, py = p / W, px = p - py * W;
+  const size_t sstride = (size_t)B * 18 * HW;
+  const float* yb = yp + (size_t)b * 18 * HW;
+  float v[9][kFhSlabs][2];
+  unsigned inm = 0u;  // taps whose neighbour is inside the image (the others load the pixel itself and add nothing)
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) {
+    const int yy = py + tap / 3 - 1, xx = px + tap % 3 - 1;
+    const bool in = static_cast<unsigned>(yy) < static_cast<unsigned>(H) && static_cast<unsigned>(xx) < static_cast<unsigned>(W);
+    inm |= (in ? 1u : 0u) << tap;
+    const int q = in ? yy * W + xx : p;
+#pragma unroll
+    for (int sl = 0; sl < kFhSlabs; ++sl)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) v[tap][sl][c] = yb[sl * sstride + (size_t)(tap * 2 + c) * HW + q];
+  }
+  float s[2] = {0.f, 0.f};
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+    for (int sl = 0; sl < kFhSlabs; ++sl)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) s[c] += ((inm >> tap) & 1u) ? v[tap][sl][c] : 0.f;
+  float* cb = coords + (size_t)b * 2 * HW + p;
+  const float c0 = cb[0] + (s[0] + bias[0]);  // coords1 = coords1 + delta_flow (raft.py:133), delta incl. conv2's bias
+  const float c1 = cb[HW] + (s[1] + bias[1]);
+  cb[0] = c0;
+  cb[HW] = c1;
+  if (!d0 && !d1) return;
+  const float fx = c0 - static_cast<float>(px), fy = c1 - static_cast<float>(py);
+  range_guard(fmaxf(fabsf(fx), fabsf(fy)));
+  _Float16 hx, lx, hy, ly;
+  split_f16(fx, hx, lx);
+  split_f16(fy, hy, ly);
+  for (int d = 0; d < 2; ++d) {
+    uint8_t* dst = d == 0 ? (d0 ? d0 + (long long)t * d0ps : nullptr) : (d1 ? d1 + (long long)t * d1ps : nullptr);
+    if (!dst) continue;
+    _Float16* h = reinterpret_cast<_Float16*>(dst);
+    h[0] = hx;
+    h[1] = hy;
+    h[32] = lx;
+    h[33] = ly;
+  }
+}
+
 }  // namespace
 OFLOW_RANGE_FLAG_SETTER(s32io)
 }  // namespace oflow
@@ -616,6 +678,21 @@ extern "C" int oflow_flow_head_col2im_f32(const float* d_y, const float* d_bias,
   const int P = B * H * W;
   hipLaunchKernelGGL(flow_head_col2im_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      d_y, B, H, W, d_bias, d_coords);
+  return launch_status();
+}
+
+extern "C" int oflow_flow_head_finish_f32(const float* d_partial, int slabs, const float* d_bias, int B, int H, int W,
+                                          float* d_coords, void* d_flow0, long long flow0_pixel_stride, void* d_flow1,
+                                          long long flow1_pixel_stride, void* stream) {
+  if (!d_partial || !d_bias || !d_coords) return OFLOW_E_NULL;
+  if (slabs != kFhSlabs || B <= 0 || H <= 0 || W <= 0 || (long long)slabs * B * H * W * 18 >= (1LL << 31)) return OFLOW_E_SHAPE;
+  if (((uintptr_t)d_partial & 3) || ((uintptr_t)d_coords & 3) || (d_flow0 && ((uintptr_t)d_flow0 & 3)) ||
+      (d_flow1 && ((uintptr_t)d_flow1 & 3)))
+    return OFLOW_E_ALIGN;
+  const int P = B * H * W;
+  hipLaunchKernelGGL(flow_head_finish_kernel, dim3((unsigned)((P + kFhFinishNT - 1) / kFhFinishNT)), dim3(kFhFinishNT), 0,
+                     static_cast<hipStream_t>(stream), d_partial, B, H, W, d_bias, d_coords, static_cast<uint8_t*>(d_flow0), flow0_pixel_stride,
+                     static_cast<uint8_t*>(d_flow1), flow1_pixel_stride);
   return launch_status();
 }
 

@@ -73,8 +73,12 @@ for _bn in (CONV_BN, CONV_BN_SIDE):
 # step the other pair lane fills the CUs the 2-column conv leaves idle, so "conv" stays the default
 # r05: "tiled" = oflow_flow_head2_tiled_s32 (fp32 FMAs on an LDS-staged halo, 512 threads per 4 x 32 tile): step A/B
 # 18.81 vs 18.89 ms against "conv" (profiles/r05/s33_flow_head_tiled_ab.log; the first 256-thread form was 0.25 ms
-# slower, s32): the default; two channel groups per staging pass: +0.6 % on the graph bench (s37), bit-identical
-FLOW_HEAD_MODE = _env_choice("OFLOW_FLOW_HEAD_MODE", "tiled", ("tiled", "conv", "col2im"))
+# slower, s32): the default until "fused"; two channel groups per staging pass: +0.6 % on the graph bench (s37), bit-identical
+# "fused" = the output conv folded into the flow head's first conv (oflow_conv_s32_ex6, OFLOW_EPI_FLOW_HEAD): conv1's
+# epilogue forms the 18 per-tap products per 64-channel slab from its fp32 tile and never writes the 256-channel
+# activation; oflow_flow_head_finish_f32 gathers them into coords1 and writes the next iteration's flow channels, so
+# flow_prep runs once per forward (11 kernels per lane iteration instead of 12). DESIGN.md §4 has the measurements.
+FLOW_HEAD_MODE = _env_choice("OFLOW_FLOW_HEAD_MODE", "fused", ("fused", "tiled", "conv", "col2im"))
 # convf1 (7x7, 2 -> 128) straight from coords1 (_native.FlowIn, OFLOW_IN_FLOW7: each tile stages its flow window and
 # builds the patch operand in LDS) from this many pixels of the whole forward's batch up; below it flow_prep writes the
 # patch matrix and convf1 runs on the small-grid tiles. Bit-identical either way (same patch values, same k order).
@@ -346,6 +350,10 @@ class SplitUpdate:
     convc2, convf1 (1x1 over the patches), convf2, conv (-> hx, rhx), [z|r] (-> z, r*h -> rhx),
     q (-> h, hx) for the 1x5 and the 5x1 half, flow head conv1, conv2 (coords1 += delta in its epilogue), and at the
     last iteration the mask head (1x1 conv 256 -> 576 with the x0.25 in its epilogue, fp32 NCHW).
+    Large grids, flow head mode "fused" (the default), 11 kernels per iteration: lookup + convc1, convc2, convf1
+    (straight from coords1), convf2, conv, [z|r] and q twice, flow head conv1 with conv2's per-tap products formed
+    in its epilogue (its 256-channel activation is never written), flow_head_finish (gather -> coords1 +=, and the
+    updated flow into hx / rhx); flow_prep runs before the first iteration only.
     """
 
     def __init__(self, block: BasicUpdateBlock, cnet_out: Tensor, hdim: int, side_slot: int = 0,
@@ -379,6 +387,11 @@ class SplitUpdate:
         self.fh = S(b, h, w, 8, dev)
         self.fh2y = None  # (B, 18, H, W) per-tap products of the flow head's output conv (flow_head_mode "col2im")
         self.flow_head_mode = getattr(block, "flow_head_mode", FLOW_HEAD_MODE)
+        # "fused" (large grids only): the per-tap partial sums of the flow head, one buffer per runner; flow_for = the
+        # coords1 storage whose flow the GRU inputs' flow channels hold (written by the finish kernel: flow_prep skipped)
+        self.fused_head = self.flow_head_mode == "fused" and not self.flow_head_fma
+        self.fhy = _native.flow_head_partial_empty(b, h, w, dev) if self.fused_head else None
+        self.flow_for = None
         self.hm = torch.empty((b * h * w, hdim), device=dev, dtype=torch.float32)
         self.z = torch.empty_like(self.hm)
         V = _native.S32Slice
@@ -428,6 +441,8 @@ class SplitUpdate:
             "fh2_f32": (fh.conv2.weight.detach().float().contiguous(), fh.conv2.bias.detach().float().contiguous()),
             # large grids: the same as fp32 FMAs on an LDS-staged halo (oflow_flow_head2_tiled_s32), repacked weights
             "fh2_tiled": (_native.flow_head2_tiled_weights(fh.conv2.weight), fh.conv2.bias.detach().float().contiguous()),
+            # large grids, "fused": [slab][channel][tap, output] for the flow-head epilogue of conv1 (oflow_conv_s32_ex6)
+            "fh2_fused": _native.flow_head_fused_weights(fh.conv2.weight),
             "m1": CW(block.mask[0].weight, block.mask[0].bias, 256),
             "m2": CW(block.mask[2].weight, block.mask[2].bias, 576),
         }
@@ -489,17 +504,25 @@ class SplitUpdate:
         side = self.side_stream if self.streams else None
         bns = CONV_BN_SIDE if side is not None else CONV_BN  # (channel blocks: see CONV_BN)
         f1_in = V(self.pm) if self.pm is not None else _native.FlowIn(coords1)
+        # "fused" flow head: the previous iteration's finish kernel already wrote this coords1's flow channels (the
+        # patch matrix of small convf1 grids still needs flow_prep). coords1 must then be advanced by update() alone.
+        fused = self.fused_head and coords1.is_contiguous()
+        flow_key = (coords1.data_ptr(), tuple(coords1.shape))
+        prep = self.pm is not None or not fused or self.flow_for != flow_key
+        self.flow_for = None
         if side is not None:
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                _native.flow_prep(coords1, self.pm, (V(self.hx), 254), (V(self.rhx), 254))
+                if prep:
+                    _native.flow_prep(coords1, self.pm, (V(self.hx), 254), (V(self.rhx), 254))
                 conv(f1_in, w["f1"], bns["f1"], "relu", y0=V(self.f1))
                 conv(V(self.f1), w["f2"], bns["f2"], "relu", y0=V(self.cf, 6, 2))
             self._convc1(corr_in)
             conv(V(self.c1), w["c2"], bns["c2"], "relu", y0=V(self.cf, 0, 6))
             main.wait_stream(side)
         else:
-            _native.flow_prep(coords1, self.pm, (V(self.hx), 254), (V(self.rhx), 254))
+            if prep:
+                _native.flow_prep(coords1, self.pm, (V(self.hx), 254), (V(self.rhx), 254))
             self._convc1(corr_in)
             conv(V(self.c1), w["c2"], bns["c2"], "relu", y0=V(self.cf, 0, 6))
             conv(f1_in, w["f1"], bns["f1"], "relu", y0=V(self.f1))
@@ -511,6 +534,13 @@ class SplitUpdate:
             conv(V(self.rhx), w["q" + tag], bns["gru"], epilogue=2, y0=V(self.hx, 0, 4), gru_h=self.hm, gru_z=self.z,
                  addend=gx[:, 256:], ksplit=self.ks_q)
         net = V(self.hx, 0, 4)
+        if fused:
+            # conv1 with the flow-head epilogue, then the gather: coords1 += conv2(relu(conv1(net))) (raft.py:133) and
+            # the updated flow into the GRU inputs
+            _native.conv_s32_flow_head(net, w["fh1"], bns["fh1"], w["fh2_fused"], self.fhy)
+            _native.flow_head_finish(self.fhy, w["fh2_bias"], coords1, (V(self.hx), 254), (V(self.rhx), 254))
+            self.flow_for = flow_key
+            return self._mask(net, coords1, mask_out) if need_mask else None
         conv(net, w["fh1"], bns["fh1"], "relu", y0=V(self.fh))
         if self.flow_head_fma and coords1.is_contiguous():
             _native.flow_head2(V(self.fh), *w["fh2_f32"], coords1)  # coords1 += conv2(.) (raft.py:133)
@@ -523,8 +553,12 @@ class SplitUpdate:
             _native.flow_head_col2im(self.fh2y, w["fh2_bias"], coords1)  # coords1 += conv2(.) (raft.py:133)
         else:
             conv(V(self.fh), w["fh2"], 32, f32=coords1, f32_accumulate=True)
-        if not need_mask:
-            return None
+        return self._mask(net, coords1, mask_out) if need_mask else None
+
+    def _mask(self, net, coords1: Tensor, mask_out: Optional[Tensor]) -> Tensor:
+        """The mask head x0.25 (`update.py:159-161`), through the fh buffer."""
+        V, conv, w = _native.S32Slice, _native.conv_s32, self.w
+        b, h, wd = self.shape
         mask = mask_out if mask_out is not None else torch.empty((b, 576, h, wd), device=coords1.device, dtype=torch.float32)
         conv(net, w["m1"], 128, "relu", y0=V(self.fh))
         conv(V(self.fh), w["m2"], 64, out_scale=0.25, f32=mask)

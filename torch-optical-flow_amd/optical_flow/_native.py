@@ -79,6 +79,8 @@ SYMBOLS = (
     "oflow_set_range_flag",
     "oflow_range_flag_exchange",
     "oflow_flow_head_col2im_f32",
+    "oflow_conv_s32_ex6",
+    "oflow_flow_head_finish_f32",
     "oflow_timing_event_create",
     "oflow_timing_event_destroy",
     "oflow_timing_event_record",
@@ -285,6 +287,10 @@ def load() -> ctypes.CDLL:
     lib.oflow_timing_event_elapsed_ms.argtypes = [P, P, ctypes.POINTER(ctypes.c_float)]
     lib.oflow_flow_head_col2im_f32.restype = I
     lib.oflow_flow_head_col2im_f32.argtypes = [P, P, I, I, I, P, P]
+    lib.oflow_conv_s32_ex6.restype = I
+    lib.oflow_conv_s32_ex6.argtypes = list(lib.oflow_conv_s32_ex5.argtypes[:-1]) + [P, P, I, P]
+    lib.oflow_flow_head_finish_f32.restype = I
+    lib.oflow_flow_head_finish_f32.argtypes = [P, I, P, I, I, I, P, P, L, P, L, P]
     v = lib.oflow_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liboflow_hip.so ABI version {v}, expected {ABI_VERSION}: rebuild the library")
@@ -1191,6 +1197,85 @@ def flow_head_col2im(y: torch.Tensor, bias: torch.Tensor, coords: torch.Tensor) 
         raise RuntimeError(f"{what}: bias must be fp32 (2,) on the coords' device")
     with torch.cuda.device(coords.device), _Timed("flow_head_col2im", coords.device):
         _check(load().oflow_flow_head_col2im_f32(y.data_ptr(), bias.data_ptr(), b, h, w, coords.data_ptr(),
+                                                 _stream(coords.device)), what)
+
+
+FLOW_HEAD_SLABS = 4  # 64-channel slabs of the flow head's 256 hidden channels (oflow_conv_s32_ex6)
+
+
+def flow_head_fused_weights(weight: torch.Tensor) -> torch.Tensor:
+    """The flow head's output conv weight (2, 256, 3, 3) -> the [slab 4][channel 64][t*2 + c] fp32 copy the flow-head
+    epilogue reads (oflow_conv_s32_ex6), t = ky*3 + kx."""
+    if tuple(weight.shape) != (2, 64 * FLOW_HEAD_SLABS, 3, 3):
+        raise RuntimeError(f"flow_head_fused_weights: weight must be (2, {64 * FLOW_HEAD_SLABS}, 3, 3)")
+    return weight.detach().float().permute(1, 2, 3, 0).reshape(FLOW_HEAD_SLABS, 64, 18).contiguous()
+
+
+def flow_head_partial_empty(b: int, h: int, w: int, device) -> torch.Tensor:
+    """The flow-head epilogue's partial sums [4 slabs, B, 18, H, W] fp32 (uninitialised: every call writes all of it)."""
+    return torch.empty((FLOW_HEAD_SLABS, b, 18, h, w), device=device, dtype=torch.float32)
+
+
+def conv_s32_flow_head(x: "S32Slice", cw: "ConvWeights", block_n: int, w2r: torch.Tensor, partial) -> None:
+    """The flow head's first conv (3x3 -> 256, ReLU) with the 256 -> 2 output conv's per-tap products formed in its
+    epilogue (oflow_conv_s32_ex6, OFLOW_EPI_FLOW_HEAD): writes ``partial`` [4, B, 18, H, W] and nothing else;
+    ``flow_head_finish`` completes coords1 += conv2(relu(conv1(x))). cw: conv1's ConvWeights; w2r:
+    flow_head_fused_weights(conv2.weight); block_n 64 (LDS-staged weights) or 128 (register-direct)."""
+    what = "conv_s32_flow_head"
+    if x.ng != cw.kg:
+        raise RuntimeError(f"{what}: input has {x.ng} groups, weights expect {cw.kg}")
+    b, h, w = x.bhw
+    dev = x.device
+    if (w2r.dtype != torch.float32 or not w2r.is_contiguous() or tuple(w2r.shape[1:]) != (64, 18) or w2r.device != dev):
+        raise RuntimeError(f"{what}: w2r must be flow_head_fused_weights(conv2.weight) on the input's device")
+    slabs, pp = 0, None
+    if partial is not None:
+        if (partial.dtype != torch.float32 or not partial.is_contiguous() or partial.dim() != 5
+                or tuple(partial.shape[1:]) != (b, 18, h, w) or partial.device != dev):
+            raise RuntimeError(f"{what}: partial must be contiguous fp32 (slabs, {b}, 18, {h}, {w}) on the input's device")
+        slabs, pp = int(partial.shape[0]), partial.data_ptr()
+    if w2r.shape[0] != FLOW_HEAD_SLABS:
+        slabs = -1  # (a weight copy of another slab count: the entry reports the shape error)
+    wf = cw.frag().data_ptr() if int(block_n) == 128 and cw.layout == "conv" else None
+    if _flops is not None:
+        n_exec = -(-cw.n_pad // int(block_n)) * int(block_n)
+        _count(3 * 2 * b * h * w * n_exec * cw.kg * 32 * 9, 2 * b * h * w * cw.n * cw.cin * 9)
+        fl = 2 * b * h * w * 2 * cw.n * 9
+        _count(0, fl, fl)
+    with torch.cuda.device(dev), _Timed("conv3x3", dev):
+        _check(
+            load().oflow_conv_s32_ex6(
+                x.ptr, x.ps, cw.kg, cw.pack.data_ptr(), cw.n_pad, cw.wscale.data_ptr(),
+                cw.bias.data_ptr() if cw.bias is not None else None, cw.n, b, h, w, cw.kh, cw.kw, int(block_n),
+                3, ACT["relu"], 1.0, None, 0, None, 0, None, 0, 0, 0, None, None, 0, None, cw.n, None, None, 0, 0, 0,
+                0, None, None, None, 0, wf, None, None, 0, w2r.data_ptr(), pp, slabs, _stream(dev),
+            ),
+            what,
+        )
+
+
+def flow_head_finish(partial: torch.Tensor, bias: torch.Tensor, coords: torch.Tensor, flow0=None, flow1=None) -> None:
+    """coords (B, 2, H, W) += bias + the 3x3 gather over the taps and slabs of ``partial`` (conv_s32_flow_head's output),
+    then the updated flow = coords - pixel grid into the GRU inputs' flow channels (oflow_flow_head_finish_f32): the
+    bytes ``flow_prep(coords, None, flow0, flow1)`` would write. flow0/flow1: (S32Slice, channel) pairs or None."""
+    what = "flow_head_finish"
+    if (coords.dtype != torch.float32 or coords.dim() != 4 or coords.shape[1] != 2 or not coords.is_contiguous()
+            or coords.device.type != "cuda"):
+        raise RuntimeError(f"{what}: coords must be contiguous fp32 (B, 2, H, W) on the GPU")
+    b, _, h, w = coords.shape
+    if (partial.dtype != torch.float32 or not partial.is_contiguous() or partial.dim() != 5
+            or tuple(partial.shape[1:]) != (b, 18, h, w) or partial.device != coords.device):
+        raise RuntimeError(f"{what}: partial must be contiguous fp32 (slabs, {b}, 18, {h}, {w})")
+    if bias is None or bias.dtype != torch.float32 or tuple(bias.shape) != (2,) or bias.device != coords.device:
+        raise RuntimeError(f"{what}: bias must be fp32 (2,) on the coords' device")
+    for fl in (flow0, flow1):
+        if fl is not None and (fl[0].bhw != (b, h, w) or fl[0].device != coords.device):
+            raise RuntimeError(f"{what}: flow destination shape/device mismatch")
+    f0 = (flow0[0].channel_ptr(flow0[1]), flow0[0].ps) if flow0 is not None else (None, 0)
+    f1 = (flow1[0].channel_ptr(flow1[1]), flow1[0].ps) if flow1 is not None else (None, 0)
+    with torch.cuda.device(coords.device), _Timed("flow_head_finish", coords.device):
+        _check(load().oflow_flow_head_finish_f32(partial.data_ptr(), int(partial.shape[0]), bias.data_ptr(), b, h, w,
+                                                 coords.data_ptr(), f0[0], f0[1], f1[0], f1[1],
                                                  _stream(coords.device)), what)
 
 
