@@ -21,6 +21,10 @@
  *   oflow_convex_upsample_f32 <- methods/raft/model/raft.py:73-85 (RAFT.upsample_flow)
  *   oflow_flow_stats_f32, oflow_flow2rgb_f32 <- optical_flow/visualization/flow2rgb.py:19-73 (+ visualization/methods/)
  *   oflow_flow_pack_f32     <- optical_flow/io/middlebury.py:43-71, optical_flow/io/pfm.py:79-104 (file payloads)
+ *   oflow_flow_error_stats_f32 <- optical_flow/metrics/epe.py:24-65 (AverageEndPointError.update, end_point_error)
+ *                              + optical_flow/metrics/f1.py:34-55 (OutlierRatio.update)
+ *   oflow_sequence_loss_f32, oflow_sequence_loss_backward_f32 <- methods/raft/model/raft.py:231-260 (sequence_loss
+ *                              and its autograd)
  */
 #ifndef OFLOW_H_
 #define OFLOW_H_
@@ -484,6 +488,49 @@ int oflow_flow2rgb_f32(const float* d_flow, int B, int H, int W, int method, int
                        int invert_y, int have_denom, float denom, const float* d_partials, float* d_rgb, void* stream);
 int oflow_flow_pack_f32(const float* d_flow, int B, int H, int W, int channels, int flip_rows, float* d_out,
                         void* stream);
+
+/*
+ * Evaluation metrics and the training loss as fused streaming reductions (optical_flow/metrics/epe.py:24-65,
+ * optical_flow/metrics/f1.py:34-55, methods/raft/model/raft.py:231-260; csrc/flow_metrics.hip). Each is a partial
+ * kernel of at most OFLOW_FLOW_METRICS_PARTIALS workgroups, one row of 8 doubles each in d_workspace
+ * (>= OFLOW_FLOW_METRICS_PARTIALS * 8 doubles, 8-B aligned, any contents), and a one-workgroup finalize kernel that sums
+ * the rows in a fixed order: no float atomics, results bit-reproducible from run to run, no host synchronisation.
+ *
+ * oflow_flow_error_stats_f32: d_pred, d_target (B, 2, H, W) fp32 views with batch / channel / row strides in elements
+ *   (W stride 1; a cropped view such as InputPadder.unpad's is read in place). d_valid: (B, H, W) with batch / row
+ *   strides, valid_kind OFLOW_VALID_NONE (d_valid ignored), _F32 or _U8 (1-byte bool / uint8, non-zero = 1). Per pixel
+ *   in fp32, no contraction: dx = p0 - t0, dy = p1 - t1, epe = sqrt(dx*dx + dy*dy), mag = sqrt(t0*t0 + t1*t1),
+ *   keep = (valid >= 0.5) && (mag < max_flow, only when max_flow is positive and finite),
+ *   outlier = (epe > abs_threshold) && (epe / mag > rel_threshold) with a true division (mag == 0: an outlier when
+ *   epe > abs_threshold; 0 / 0 and a NaN prediction are not). Over the kept pixels
+ *     d_accum[0..5] += {sum epe, n, n_outlier, n(epe < 1), n(epe < 3), n(epe < 5)}   (fp64; d_accum[6..7] untouched)
+ *   so one accumulator serves any number of calls; d_epe_map (NULL: none): contiguous (B, H, W) fp32, epe of EVERY pixel.
+ *   16-B loads when every base and stride allows, coalesced dword loads otherwise.
+ * oflow_sequence_loss_f32: d_preds: host array of n_preds (1..OFLOW_MAX_PREDS) device pointers to contiguous
+ *   (B, 2, H, W) fp32 predictions, weights: n_preds HOST floats (gamma^(n - i - 1)), d_flow_gt (B, 2, H, W), d_valid
+ *   (B, H, W) of kind _F32 or _U8, all contiguous. mask = (valid >= 0.5) && (mag_gt < max_flow);
+ *   d_loss[0] = fp32(sum_i w_i * sum mask * (|dx_i| + |dy_i|) / (2 B H W)) (the mask multiplies: NaN under it propagates);
+ *   d_stats[0..7] = {n_valid, n(epe < 1), n(epe < 3), n(epe < 5), sum epe, the fp64 loss sum, 0, 0} of the LAST prediction
+ *   over the masked pixels (written, not added).
+ * oflow_sequence_loss_backward_f32: d_grads[i] (NULL: prediction i needs none) = (gout * w_i / (2 B H W)) * mask *
+ *   sgn(pred_i - gt), sgn(0) = sgn(NaN) = 0 (ATen's abs backward); gout = d_grad_out[0], a device scalar. One launch.
+ */
+#define OFLOW_FLOW_METRICS_PARTIALS 1024
+#define OFLOW_MAX_PREDS 32
+#define OFLOW_VALID_NONE 0
+#define OFLOW_VALID_F32 1
+#define OFLOW_VALID_U8 2
+int oflow_flow_error_stats_f32(const float* d_pred, long long pred_sb, long long pred_sc, long long pred_sh,
+                               const float* d_target, long long target_sb, long long target_sc, long long target_sh,
+                               const void* d_valid, int valid_kind, long long valid_sb, long long valid_sh, int B, int H,
+                               int W, float abs_threshold, float rel_threshold, float max_flow, float* d_epe_map,
+                               double* d_workspace, double* d_accum, void* stream);
+int oflow_sequence_loss_f32(const float* const* d_preds, int n_preds, const float* weights, const float* d_flow_gt,
+                            const void* d_valid, int valid_kind, int B, int H, int W, float max_flow,
+                            double* d_workspace, float* d_loss, double* d_stats, void* stream);
+int oflow_sequence_loss_backward_f32(const float* d_grad_out, const float* const* d_preds, float* const* d_grads,
+                                     int n_preds, const float* weights, const float* d_flow_gt, const void* d_valid,
+                                     int valid_kind, int B, int H, int W, float max_flow, void* stream);
 
 #ifdef __cplusplus
 }

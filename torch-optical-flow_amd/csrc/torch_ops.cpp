@@ -19,13 +19,18 @@
 //   corr_pyramid_backward(level_grads, fmap1, fmap2) -> (g1, g2)  pool transpose + two fp32-MFMA GEMMs
 //   grid_warp_backward(grad_out, frame, flow, mode, pad, ac, mask) -> (grad_frame, grad_flow)     warp's autograd
 //   grid_sample_backward(grad_out, input, grid, mode, pad, ac, mask) -> (grad_input, grad_grid)   grid_sample's autograd
+//   flow_error_stats(pred, target, valid?, abs, rel, max_flow, accum!, epe_map) -> Tensor   metrics/epe.py:24-65, f1.py:34-55
+//   sequence_loss(flow_preds, flow_gt, valid, weights, max_flow) -> (loss, stats)           raft.py:231-260 (forward)
+//   sequence_loss_backward(grad_out, flow_preds, flow_gt, valid, weights, max_flow, need) -> Tensor[]   its autograd
 #include <array>
 #include <torch/library.h>
 #include <ATen/ATen.h>
 #include <ATen/hip/HIPContext.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 
+#include <climits>
 #include <cmath>
+#include <limits>
 #include <vector>
 
 #include "oflow.h"
@@ -549,6 +554,177 @@ std::tuple<Tensor, Tensor> pyramid_backward_meta(const std::vector<Tensor>& g, c
   return pyramid_backward_impl(g, f1, f2, false);
 }
 
+// ---------------------------------------------------------------- metrics / sequence loss (flow_metrics.hip)
+const char* kNoCpu = "; this MI355X build runs only on ROCm GPU tensors (no CPU fallback)";
+
+void check_flow_pair(const Tensor& pred, const Tensor& target, const char* what) {
+  TORCH_CHECK(pred.dim() == 4 && pred.size(1) == 2 && pred.sizes() == target.sizes(), what, ": pred ", pred.sizes(),
+              " and target ", target.sizes(), " must be equal (B, 2, H, W)");
+  TORCH_CHECK(pred.device() == target.device(), what, ": pred and target are on different devices");
+  TORCH_CHECK(pred.size(0) <= INT_MAX && pred.size(2) <= INT_MAX && pred.size(3) <= INT_MAX, what, ": a size exceeds 2^31");
+}
+
+// fp32 with unit stride along W; batch / channel / row strides stay as they are (a cropped view is read in place)
+Tensor strided_f32(const Tensor& t) {
+  Tensor f = t.scalar_type() == at::kFloat ? t : t.to(at::kFloat);
+  return (f.size(3) > 1 && f.stride(3) != 1) ? f.contiguous() : f;
+}
+
+struct ValidArg {
+  Tensor t;
+  int kind = OFLOW_VALID_NONE;
+  int64_t sb = 0, sh = 0;
+  const void* ptr() const { return kind == OFLOW_VALID_NONE ? nullptr : t.data_ptr(); }
+};
+
+void check_valid(const Tensor& v, const Tensor& flow, const char* what) {
+  TORCH_CHECK(v.numel() == flow.size(0) * flow.size(2) * flow.size(3), what, ": valid ", v.sizes(),
+              " must have one element per pixel of ", flow.sizes());
+  TORCH_CHECK(v.device() == flow.device(), what, ": valid is on another device than the flow");
+}
+
+// valid as (B, H, W) with unit W stride: bool / uint8 as they are (1 byte), anything else as fp32
+ValidArg valid_arg(const Tensor& valid, const Tensor& flow, bool need_contiguous) {
+  ValidArg a;
+  const int64_t b = flow.size(0), h = flow.size(2), w = flow.size(3);
+  const bool bytes = valid.scalar_type() == at::kBool || valid.scalar_type() == at::kByte;
+  Tensor v = (bytes || valid.scalar_type() == at::kFloat) ? valid : valid.to(at::kFloat);
+  if (v.dim() == 4 && v.size(1) == 1) v = v.select(1, 0);
+  const bool shaped = v.dim() == 3 && v.size(0) == b && v.size(1) == h && v.size(2) == w && (w == 1 || v.stride(2) == 1);
+  if (!shaped || need_contiguous) v = v.reshape({b, h, w}).contiguous();
+  a.t = v;
+  a.kind = bytes ? OFLOW_VALID_U8 : OFLOW_VALID_F32;
+  a.sb = v.stride(0);
+  a.sh = v.stride(1);
+  return a;
+}
+
+Tensor flow_error_stats_impl(const Tensor& pred, const Tensor& target, const c10::optional<Tensor>& valid, double abs_t,
+                             double rel_t, double max_flow, const Tensor& accum, bool epe_map, bool run) {
+  const char* what = "flow_error_stats";
+  check_flow_pair(pred, target, what);
+  if (valid.has_value()) check_valid(*valid, pred, what);
+  TORCH_CHECK(accum.scalar_type() == at::kDouble && accum.dim() == 1 && accum.size(0) == 8 && accum.is_contiguous() &&
+                  accum.device() == pred.device(),
+              what, ": the accumulator must be a contiguous float64 [8] on the flow's device, got ", accum.sizes());
+  const int64_t b = pred.size(0), h = pred.size(2), w = pred.size(3);
+  const auto fopt = pred.options().dtype(at::kFloat);
+  if (!run) return epe_map ? at::empty({b, h, w}, fopt) : at::empty({0}, fopt);
+  TORCH_CHECK(pred.is_cuda(), what, ": pred is on ", pred.device(), kNoCpu);
+  Tensor map = epe_map ? at::empty({b, h, w}, fopt) : at::empty({0}, fopt);
+  if (b * h * w == 0) return map;
+  Tensor pr = strided_f32(pred), tg = strided_f32(target);
+  ValidArg va;
+  if (valid.has_value()) va = valid_arg(*valid, pr, false);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(pr.device());
+  Tensor ws = at::empty({OFLOW_FLOW_METRICS_PARTIALS * 8}, pr.options().dtype(at::kDouble));
+  check_status(oflow_flow_error_stats_f32(pr.data_ptr<float>(), pr.stride(0), pr.stride(1), pr.stride(2),
+                                          tg.data_ptr<float>(), tg.stride(0), tg.stride(1), tg.stride(2), va.ptr(), va.kind,
+                                          va.sb, va.sh, (int)b, (int)h, (int)w, (float)abs_t, (float)rel_t, (float)max_flow,
+                                          epe_map ? map.data_ptr<float>() : nullptr, ws.data_ptr<double>(),
+                                          accum.data_ptr<double>(), cur_stream()),
+               what);
+  return map;
+}
+Tensor flow_error_stats_hip(const Tensor& p, const Tensor& t, const c10::optional<Tensor>& v, double a, double r, double m,
+                            const Tensor& acc, bool map) {
+  return flow_error_stats_impl(p, t, v, a, r, m, acc, map, true);
+}
+Tensor flow_error_stats_meta(const Tensor& p, const Tensor& t, const c10::optional<Tensor>& v, double a, double r, double m,
+                             const Tensor& acc, bool map) {
+  return flow_error_stats_impl(p, t, v, a, r, m, acc, map, false);
+}
+
+void check_loss_args(const std::vector<Tensor>& preds, const Tensor& gt, const Tensor& valid, at::ArrayRef<double> weights,
+                     const char* what) {
+  const int64_t n = (int64_t)preds.size();
+  TORCH_CHECK(n >= 1 && n <= OFLOW_MAX_PREDS, what, ": number of flow predictions ", n, " outside [1, ", OFLOW_MAX_PREDS, "]");
+  TORCH_CHECK((int64_t)weights.size() == n, what, ": ", weights.size(), " weights for ", n, " predictions");
+  for (int64_t i = 0; i < n; ++i) check_flow_pair(preds[i], gt, what);
+  check_valid(valid, gt, what);
+}
+
+std::tuple<Tensor, Tensor> sequence_loss_impl(const std::vector<Tensor>& preds, const Tensor& gt, const Tensor& valid,
+                                              at::ArrayRef<double> weights, double max_flow, bool run) {
+  const char* what = "sequence_loss";
+  check_loss_args(preds, gt, valid, weights, what);
+  Tensor loss = at::empty({}, gt.options().dtype(at::kFloat)), stats = at::empty({8}, gt.options().dtype(at::kDouble));
+  if (!run) return {loss, stats};
+  TORCH_CHECK(gt.is_cuda(), what, ": flow_gt is on ", gt.device(), kNoCpu);
+  const int64_t b = gt.size(0), h = gt.size(2), w = gt.size(3), n = (int64_t)preds.size();
+  if (b * h * w == 0)  // the mean of no elements
+    return {loss.fill_(std::numeric_limits<float>::quiet_NaN()), stats.zero_()};
+  Tensor g32 = gpu_f32(gt, "flow_gt", what);
+  ValidArg va = valid_arg(valid, g32, true);
+  std::vector<Tensor> keep;
+  const float* ptrs[OFLOW_MAX_PREDS];
+  float wts[OFLOW_MAX_PREDS];
+  for (int64_t i = 0; i < n; ++i) {
+    keep.push_back(gpu_f32(preds[i], "flow_preds", what));
+    ptrs[i] = keep.back().data_ptr<float>();
+    wts[i] = (float)weights[i];
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA g(g32.device());
+  Tensor ws = at::empty({OFLOW_FLOW_METRICS_PARTIALS * 8}, stats.options());
+  check_status(oflow_sequence_loss_f32(ptrs, (int)n, wts, g32.data_ptr<float>(), va.ptr(), va.kind, (int)b, (int)h, (int)w,
+                                       (float)max_flow, ws.data_ptr<double>(), loss.data_ptr<float>(),
+                                       stats.data_ptr<double>(), cur_stream()),
+               what);
+  return {loss, stats};
+}
+std::tuple<Tensor, Tensor> sequence_loss_hip(const std::vector<Tensor>& p, const Tensor& gt, const Tensor& v,
+                                             at::ArrayRef<double> w, double m) {
+  return sequence_loss_impl(p, gt, v, w, m, true);
+}
+std::tuple<Tensor, Tensor> sequence_loss_meta(const std::vector<Tensor>& p, const Tensor& gt, const Tensor& v,
+                                              at::ArrayRef<double> w, double m) {
+  return sequence_loss_impl(p, gt, v, w, m, false);
+}
+
+// one gradient per prediction; a prediction with need[i] == 0 gets an empty (0-element) tensor and the kernel a null
+// pointer for it (nothing read or written for that prediction)
+std::vector<Tensor> sequence_loss_backward_impl(const Tensor& gout, const std::vector<Tensor>& preds, const Tensor& gt,
+                                                const Tensor& valid, at::ArrayRef<double> weights, double max_flow,
+                                                at::IntArrayRef need, bool run) {
+  const char* what = "sequence_loss backward";
+  check_loss_args(preds, gt, valid, weights, what);
+  const int64_t n = (int64_t)preds.size();
+  TORCH_CHECK((int64_t)need.size() == n, what, ": ", need.size(), " gradient flags for ", n, " predictions");
+  TORCH_CHECK(gout.numel() == 1 && gout.device() == gt.device(), what, ": grad_out must be one element on the flow's device");
+  const auto fopt = gt.options().dtype(at::kFloat);
+  std::vector<Tensor> grads;
+  for (int64_t i = 0; i < n; ++i) grads.push_back(need[i] ? at::empty(gt.sizes(), fopt) : at::empty({0}, fopt));
+  if (!run) return grads;
+  TORCH_CHECK(gt.is_cuda(), what, ": flow_gt is on ", gt.device(), kNoCpu);
+  const int64_t b = gt.size(0), h = gt.size(2), w = gt.size(3);
+  if (b * h * w == 0) return grads;
+  Tensor g32 = gpu_f32(gt, "flow_gt", what), go = gpu_f32(gout, "grad_out", what).reshape({1});
+  ValidArg va = valid_arg(valid, g32, true);
+  std::vector<Tensor> keep;
+  const float* ptrs[OFLOW_MAX_PREDS];
+  float* gptrs[OFLOW_MAX_PREDS];
+  float wts[OFLOW_MAX_PREDS];
+  for (int64_t i = 0; i < n; ++i) {
+    keep.push_back(gpu_f32(preds[i], "flow_preds", what));
+    ptrs[i] = keep.back().data_ptr<float>();
+    gptrs[i] = need[i] ? grads[i].data_ptr<float>() : nullptr;
+    wts[i] = (float)weights[i];
+  }
+  c10::hip::HIPGuardMasqueradingAsCUDA g(g32.device());
+  check_status(oflow_sequence_loss_backward_f32(go.data_ptr<float>(), ptrs, gptrs, (int)n, wts, g32.data_ptr<float>(),
+                                                va.ptr(), va.kind, (int)b, (int)h, (int)w, (float)max_flow, cur_stream()),
+               what);
+  return grads;
+}
+std::vector<Tensor> sequence_loss_backward_hip(const Tensor& go, const std::vector<Tensor>& p, const Tensor& gt, const Tensor& v,
+                                               at::ArrayRef<double> w, double m, at::IntArrayRef need) {
+  return sequence_loss_backward_impl(go, p, gt, v, w, m, need, true);
+}
+std::vector<Tensor> sequence_loss_backward_meta(const Tensor& go, const std::vector<Tensor>& p, const Tensor& gt, const Tensor& v,
+                                                at::ArrayRef<double> w, double m, at::IntArrayRef need) {
+  return sequence_loss_backward_impl(go, p, gt, v, w, m, need, false);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(oflow, m) {
@@ -565,6 +741,9 @@ TORCH_LIBRARY(oflow, m) {
   m.def("corr_pyramid_backward(Tensor[] level_grads, Tensor fmap1, Tensor fmap2) -> (Tensor, Tensor)");
   m.def("grid_warp_backward(Tensor grad_out, Tensor frame, Tensor flow, int mode, int padding_mode, bool align_corners, bool[2] output_mask) -> (Tensor, Tensor)");
   m.def("grid_sample_backward(Tensor grad_out, Tensor input, Tensor grid, int mode, int padding_mode, bool align_corners, bool[2] output_mask) -> (Tensor, Tensor)");
+  m.def("flow_error_stats(Tensor pred, Tensor target, Tensor? valid, float abs_threshold, float rel_threshold, float max_flow, Tensor(a!) accum, bool epe_map) -> Tensor");
+  m.def("sequence_loss(Tensor[] flow_preds, Tensor flow_gt, Tensor valid, float[] weights, float max_flow) -> (Tensor, Tensor)");
+  m.def("sequence_loss_backward(Tensor grad_out, Tensor[] flow_preds, Tensor flow_gt, Tensor valid, float[] weights, float max_flow, int[] need) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
@@ -581,6 +760,9 @@ TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
   m.impl("corr_pyramid_backward", &pyramid_backward_hip);
   m.impl("grid_warp_backward", &grid_warp_backward_hip);
   m.impl("grid_sample_backward", &grid_sample_backward_hip);
+  m.impl("flow_error_stats", &flow_error_stats_hip);
+  m.impl("sequence_loss", &sequence_loss_hip);
+  m.impl("sequence_loss_backward", &sequence_loss_backward_hip);
 }
 
 // CPU tensors reach the same kernels, whose first check raises "no CPU fallback" (there is no CPU path)
@@ -598,6 +780,9 @@ TORCH_LIBRARY_IMPL(oflow, CPU, m) {
   m.impl("corr_pyramid_backward", &pyramid_backward_hip);
   m.impl("grid_warp_backward", &grid_warp_backward_hip);
   m.impl("grid_sample_backward", &grid_sample_backward_hip);
+  m.impl("flow_error_stats", &flow_error_stats_hip);
+  m.impl("sequence_loss", &sequence_loss_hip);
+  m.impl("sequence_loss_backward", &sequence_loss_backward_hip);
 }
 
 TORCH_LIBRARY_IMPL(oflow, Meta, m) {
@@ -614,4 +799,7 @@ TORCH_LIBRARY_IMPL(oflow, Meta, m) {
   m.impl("corr_pyramid_backward", &pyramid_backward_meta);
   m.impl("grid_warp_backward", &grid_warp_backward_meta);
   m.impl("grid_sample_backward", &grid_sample_backward_meta);
+  m.impl("flow_error_stats", &flow_error_stats_meta);
+  m.impl("sequence_loss", &sequence_loss_meta);
+  m.impl("sequence_loss_backward", &sequence_loss_backward_meta);
 }

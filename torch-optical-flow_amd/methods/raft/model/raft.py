@@ -1,8 +1,10 @@
 """RAFT inference model (reference: methods/raft/model/raft.py:21-147), MI355X-native correlation path.
 
 Same constructor arguments, ``hparams`` attribute, sub-modules and ``state_dict`` keys as the reference's
-LightningModule, so its checkpoints load unchanged; the training loop (`raft.py:149-260`: loss, optimizers,
-W&B logging) is out of scope. ``forward`` keeps the reference's semantics and return
+LightningModule, so its checkpoints load unchanged. Of the training / evaluation half (`raft.py:149-260`) the metrics
+(``epe_train`` / ``epe_val`` / ``f1_val``), ``validation_step`` and the module-level ``sequence_loss`` are here, on the
+fused reductions of csrc/flow_metrics.hip; the Lightning trainer hooks, optimizers and W&B logging stay out of scope
+(SURVEY.md §2 row 7). ``forward`` keeps the reference's semantics and return
 values; three output-identical changes remove host work from the loop:
   * the correlation pyramid and every lookup run on the gfx950 kernels (``model.corr.CorrBlock``);
     ``alternate_corr=True`` (an addition, default off) swaps in the volume-free fp16 ``AlternateCorrBlock``
@@ -29,11 +31,12 @@ import torch.nn.functional as F
 from torch import Tensor
 
 from optical_flow import _native
+from optical_flow.metrics import AverageEndPointError, OutlierRatio
 
 from .corr import AlternateCorrBlock, CorrBlock
 from .extractor import BasicEncoder, SplitEncoder
 from .update import BasicUpdateBlock, FusedUpdate, SplitUpdate, _side_stream, capture_active
-from .utils import coords_grid, upflow8
+from .utils import InputPadder, coords_grid, upflow8
 
 # RAFT.forward's input scaling (raft.py:104-105) through oflow_normalize_images_f32 on GPU inference: one kernel for
 # both frames, bit-identical to the reference's CPU arithmetic (ATen on the GPU divides by multiplying with fl(1/255),
@@ -97,6 +100,11 @@ class RAFT(nn.Module):
         self.fnet = BasicEncoder(output_dim=256, norm_fn="instance", dropout=dropout)
         self.cnet = BasicEncoder(output_dim=hidden_dim + context_dim, norm_fn="batch", dropout=dropout)
         self.update_block = BasicUpdateBlock(corr_levels=corr_levels, corr_radius=corr_radius, hidden_dim=hidden_dim)
+        # metrics (raft.py:55-57): modules without parameters or buffers, so the state_dict keys are the reference's
+        # without its torchmetrics states (load_from_checkpoint drops those)
+        self.epe_train = AverageEndPointError()
+        self.epe_val = AverageEndPointError()
+        self.f1_val = OutlierRatio(abs_threshold=3.0, rel_threshold=0.05)
         # plain attributes (not hparams): how GPU inference runs the update block. "split": split-fp16 matrix-core
         # convolutions with fused epilogues (SplitUpdate, default); "fused": MIOpen fp32 convolutions + fused
         # elementwise kernels (FusedUpdate); "module": the nn.Module as written. fused_update=False forces "module".
@@ -164,6 +172,20 @@ class RAFT(nn.Module):
         for m in self.modules():
             if isinstance(m, nn.BatchNorm2d):
                 m.eval()
+
+    # -- evaluation --------------------------------------------------------------------------------------
+    def validation_step(self, batch: Tuple[Tensor, Tensor, Tensor, Tensor], batch_idx: int = 0, stage: str = "sintel") -> None:
+        """One evaluation batch ``(img0, img1, flow_gt, valid)`` (`raft.py:183-196`): pad for ``stage`` (the reference
+        takes it from the trainer's datamodule), run ``hparams.iters_val`` iterations in test mode, unpad, update
+        ``epe_val`` and ``f1_val``. The metrics read the unpadded prediction as the cropped view it is (no copy) and
+        nothing here synchronises with the host; ``compute()`` on the metrics gives the result."""
+        img0, img1, flow_gt, valid = batch
+        padder = InputPadder(img0.shape, mode=stage)
+        img0, img1 = padder.pad(img0, img1)
+        _, flow_pr = self(img0, img1, iters=self.hparams.iters_val, test_mode=True)
+        flow_pr = padder.unpad(flow_pr)
+        self.epe_val.update(flow_pr, flow_gt, valid)
+        self.f1_val.update(flow_pr, flow_gt, valid)
 
     # -- forward -----------------------------------------------------------------------------------------
     @staticmethod
@@ -450,3 +472,40 @@ class RAFT(nn.Module):
         if test_mode:
             return coords1 - coords0, flow_up
         return flow_predictions
+
+
+def sequence_loss(
+    flow_preds: List[Tensor],
+    flow_gt: Tensor,
+    valid: Tensor,
+    gamma: float = 0.8,
+    max_flow: float = 400.0,
+) -> Tuple[Tensor, Dict[str, float]]:
+    """Loss function defined over a sequence of flow predictions (`raft.py:231-260`): the L1 error of every
+    prediction over the pixels with ``valid >= 0.5`` and ``|flow_gt| < max_flow``, weighted by
+    ``gamma ** (n - i - 1)``, and the shares of the last prediction's valid pixels with an end-point error under
+    1 / 3 / 5 px as Python floats.
+
+    On the GPU this is ``torch.ops.oflow.sequence_loss``: one pass over all predictions for the forward, one for
+    every gradient (differentiable in the predictions), and one 64-byte device-to-host copy for the three metrics
+    where the reference makes three ``.item()`` calls. CPU tensors run the reference's torch composition."""
+    n = len(flow_preds)
+    weights = [gamma ** (n - i - 1) for i in range(n)]
+    if flow_gt.is_cuda:
+        loss, stats = _native.ops().sequence_loss(list(flow_preds), flow_gt, valid, weights, float(max_flow))
+        s = stats.cpu()  # the one D2H copy: {n_valid, n<1, n<3, n<5, ...} as float64
+        px = (s[1:4] / s[0]).float().tolist()  # (fp32, as the reference's `.float().mean()`; NaN when nothing is valid)
+        return loss, {"1px": px[0], "3px": px[1], "5px": px[2]}
+    return sequence_loss_torch(flow_preds, flow_gt, valid, weights, max_flow)
+
+
+def sequence_loss_torch(flow_preds, flow_gt: Tensor, valid: Tensor, weights, max_flow: float):
+    """``sequence_loss`` as the reference's torch composition (`raft.py:239-258`) under autograd: the CPU path."""
+    mag = torch.sum(flow_gt**2, dim=1).sqrt()
+    mask = (valid.reshape(mag.shape) >= 0.5) & (mag < max_flow)
+    loss = 0.0
+    for w, pred in zip(weights, flow_preds):
+        loss = loss + w * (mask[:, None] * (pred - flow_gt).abs()).mean()
+    epe = torch.sum((flow_preds[-1].detach() - flow_gt) ** 2, dim=1).sqrt()[mask]
+    px = torch.stack([(epe < t).float().mean() for t in (1, 3, 5)]).tolist()
+    return loss, {"1px": px[0], "3px": px[1], "5px": px[2]}

@@ -85,6 +85,9 @@ SYMBOLS = (
     "oflow_timing_event_destroy",
     "oflow_timing_event_record",
     "oflow_timing_event_elapsed_ms",
+    "oflow_flow_error_stats_f32",
+    "oflow_sequence_loss_f32",
+    "oflow_sequence_loss_backward_f32",
 )
 
 _lib = None
@@ -291,6 +294,13 @@ def load() -> ctypes.CDLL:
     lib.oflow_conv_s32_ex6.argtypes = list(lib.oflow_conv_s32_ex5.argtypes[:-1]) + [P, P, I, P]
     lib.oflow_flow_head_finish_f32.restype = I
     lib.oflow_flow_head_finish_f32.argtypes = [P, I, P, I, I, I, P, P, L, P, L, P]
+    FP = ctypes.POINTER(F)
+    lib.oflow_flow_error_stats_f32.restype = I
+    lib.oflow_flow_error_stats_f32.argtypes = [P, L, L, L, P, L, L, L, P, I, L, L, I, I, I, F, F, F, P, P, P, P]
+    lib.oflow_sequence_loss_f32.restype = I
+    lib.oflow_sequence_loss_f32.argtypes = [PP, I, FP, P, P, I, I, I, I, F, P, P, P, P]
+    lib.oflow_sequence_loss_backward_f32.restype = I
+    lib.oflow_sequence_loss_backward_f32.argtypes = [P, PP, PP, I, FP, P, P, I, I, I, I, F, P]
     v = lib.oflow_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liboflow_hip.so ABI version {v}, expected {ABI_VERSION}: rebuild the library")

@@ -13,7 +13,12 @@ Autograd:
   * ``grid_warp`` / ``grid_sample``: the native transpose (``grid_warp_backward`` / ``grid_sample_backward``,
     csrc/warp_backward.hip: ATen grid_sampler_2d_backward's formulas, tap gradients added with fp32 atomics); the
     warp's base grid is constant, so the flow gradient is the grid gradient.
-The tiled / NHWC / fp16 on-the-fly lookups are the inference layouts and have no autograd formula.
+  * ``sequence_loss``: one native pass writes the gradient of every prediction that needs one
+    (``sequence_loss_backward``, csrc/flow_metrics.hip); flow_gt and valid get none, and the statistics output is not
+    differentiable. ``register_autograd`` handles the ``Tensor[]`` argument (a list of per-prediction gradients, None
+    where ``needs_input_grad`` is False).
+The tiled / NHWC / fp16 on-the-fly lookups are the inference layouts and have no autograd formula; ``flow_error_stats``
+(the metrics' accumulating reduction) has none either.
 """
 from __future__ import annotations
 
@@ -38,6 +43,9 @@ OPS = (
     "corr_pyramid_backward",
     "grid_warp_backward",
     "grid_sample_backward",
+    "flow_error_stats",
+    "sequence_loss",
+    "sequence_loss_backward",
 )
 _loaded = False
 
@@ -136,9 +144,26 @@ def _sample_backward(ctx, grad_out):
     return g_x, g_g, None, None, None
 
 
+def _seqloss_setup(ctx, inputs, output):
+    preds, flow_gt, valid, weights, max_flow = inputs
+    ctx.save_for_backward(flow_gt, valid, *preds)
+    ctx.args = (list(weights), max_flow)
+    ctx.mark_non_differentiable(output[1])
+
+
+def _seqloss_backward(ctx, grad_loss, _grad_stats):
+    flow_gt, valid, *preds = ctx.saved_tensors
+    weights, max_flow = ctx.args
+    need = [bool(n) for n in ctx.needs_input_grad[0]]
+    grads = torch.ops.oflow.sequence_loss_backward(grad_loss, preds, flow_gt, valid, weights, max_flow,
+                                                   [int(n) for n in need])
+    return [g.to(p.dtype) if n else None for g, p, n in zip(grads, preds, need)], None, None, None, None
+
+
 def _register_autograd() -> None:
     reg = torch.library.register_autograd
     reg("oflow::corr_pyramid", _pyramid_backward, setup_context=_pyramid_setup)
     reg("oflow::corr_lookup", _lookup_backward, setup_context=_lookup_setup)
     reg("oflow::grid_warp", _warp_backward, setup_context=_warp_setup)
     reg("oflow::grid_sample", _sample_backward, setup_context=_sample_setup)
+    reg("oflow::sequence_loss", _seqloss_backward, setup_context=_seqloss_setup)
