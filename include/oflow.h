@@ -19,6 +19,7 @@
  *   oflow_conv_s32 & co.    <- methods/raft/model/update.py:40-161 (update-block convolutions)
  *   oflow_stem_patches_s32, oflow_norm_*, oflow_conv_s32_ex <- methods/raft/model/extractor.py:35-231 (encoders)
  *   oflow_convex_upsample_f32 <- methods/raft/model/raft.py:73-85 (RAFT.upsample_flow)
+ *   oflow_convex_upsample_backward_f32 <- the same lines under autograd (the training step, raft.py:149-175)
  *   oflow_flow_stats_f32, oflow_flow2rgb_f32 <- optical_flow/visualization/flow2rgb.py:19-73 (+ visualization/methods/)
  *   oflow_flow_pack_f32     <- optical_flow/io/middlebury.py:43-71, optical_flow/io/pfm.py:79-104 (file payloads)
  *   oflow_flow_error_stats_f32 <- optical_flow/metrics/epe.py:24-65 (AverageEndPointError.update, end_point_error)
@@ -428,6 +429,19 @@ int oflow_norm_apply_s32(const float* d_x, int C, int B, int H, int W, const flo
  *   zero-padded 3x3 neighbourhood. B, H <= 65535.
  */
 int oflow_convex_upsample_f32(const float* d_flow, const float* d_mask, int B, int H, int W, float* d_out, void* stream);
+/*
+ * oflow_convex_upsample_backward_f32 (csrc/upsample_backward.hip): its autograd transpose for a training step
+ *   (raft.py:149-175). d_grad_out (B, 2, 8H, 8W), the forward's flow and mask -> d_grad_flow (B, 2, H, W) and
+ *   d_grad_mask (B, 576, H, W). The softmax is recomputed from the mask; nothing else is kept from the forward.
+ *   Either output may be NULL (that gradient is not formed: no stores of d_grad_mask, or no flow phase); both NULL is
+ *   OFLOW_E_NULL. Every element of a requested output is written (the caller zeroes nothing), with no atomics: two
+ *   calls give the same bits.
+ *   d_scratch: B * 18 * H * W floats, required when d_grad_flow is not NULL (else ignored, may be NULL); it holds the
+ *   per-pixel tap sums (B, 18, H, W) between the main pass and the nine-tap gather and needs no initialisation.
+ *   B, H <= 65535.
+ */
+int oflow_convex_upsample_backward_f32(const float* d_grad_out, const float* d_flow, const float* d_mask, int B, int H,
+                                       int W, float* d_grad_flow, float* d_grad_mask, float* d_scratch, void* stream);
 
 /*
  * Backward of the correlation (methods/raft/model/corr.py:38-87 + utils.py:64-80 under autograd, the training step

@@ -22,6 +22,8 @@
 //   flow_error_stats(pred, target, valid?, abs, rel, max_flow, accum!, epe_map) -> Tensor   metrics/epe.py:24-65, f1.py:34-55
 //   sequence_loss(flow_preds, flow_gt, valid, weights, max_flow) -> (loss, stats)           raft.py:231-260 (forward)
 //   sequence_loss_backward(grad_out, flow_preds, flow_gt, valid, weights, max_flow, need) -> Tensor[]   its autograd
+//   convex_upsample(flow, mask) -> Tensor                                                   RAFT.upsample_flow (raft.py:73-85)
+//   convex_upsample_backward(grad_out, flow, mask, mask2) -> (grad_flow, grad_mask)         its autograd
 #include <array>
 #include <torch/library.h>
 #include <ATen/ATen.h>
@@ -725,6 +727,73 @@ std::vector<Tensor> sequence_loss_backward_meta(const Tensor& go, const std::vec
   return sequence_loss_backward_impl(go, p, gt, v, w, m, need, false);
 }
 
+// ---------------------------------------------------------------- convex upsampling (upsample.hip, upsample_backward.hip)
+void check_upsample(const Tensor& flow, const Tensor& mask, const char* what) {
+  TORCH_CHECK(flow.dim() == 4 && flow.size(1) == 2 && mask.dim() == 4 && mask.size(1) == 576 &&
+                  mask.size(0) == flow.size(0) && mask.size(2) == flow.size(2) && mask.size(3) == flow.size(3),
+              what, ": flow ", flow.sizes(), " must be (B, 2, H, W) and mask ", mask.sizes(), " (B, 576, H, W)");
+  TORCH_CHECK(flow.device() == mask.device(), what, ": flow and mask are on different devices");
+  TORCH_CHECK(flow.size(0) <= 65535 && flow.size(2) <= 65535 && flow.size(3) <= INT_MAX / 8, what, ": flow ", flow.sizes(),
+              " is past the kernel's grid (B, H <= 65535, 8 W < 2^31)");
+}
+
+void check_on_gpu(const Tensor& t, const char* name, const char* what) {
+  TORCH_CHECK(t.is_cuda(), what, ": ", name, " is on ", t.device(), kNoCpu);
+}
+
+Tensor convex_upsample_impl(const Tensor& flow, const Tensor& mask, bool run) {
+  const char* what = "upsample_flow";
+  if (run) check_on_gpu(flow, "flow", what), check_on_gpu(mask, "mask", what);
+  check_upsample(flow, mask, what);
+  const int64_t b = flow.size(0), h = flow.size(2), w = flow.size(3);
+  if (!run) return at::empty({b, 2, 8 * h, 8 * w}, flow.options().dtype(at::kFloat));
+  Tensor fl = gpu_f32(flow, "flow", what), mk = gpu_f32(mask, "mask", what);
+  Tensor out = at::empty({b, 2, 8 * h, 8 * w}, fl.options());
+  if (out.numel() == 0) return out;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(fl.device());
+  check_status(oflow_convex_upsample_f32(fl.data_ptr<float>(), mk.data_ptr<float>(), (int)b, (int)h, (int)w,
+                                         out.data_ptr<float>(), cur_stream()),
+               what);
+  return out;
+}
+Tensor convex_upsample_hip(const Tensor& flow, const Tensor& mask) { return convex_upsample_impl(flow, mask, true); }
+Tensor convex_upsample_meta(const Tensor& flow, const Tensor& mask) { return convex_upsample_impl(flow, mask, false); }
+
+// (grad_flow, grad_mask); an output not wanted is an empty (0-element) tensor and the kernel gets a null pointer for it
+// (no grad_mask stores / no flow phase). The (B, 18, H, W) tap-sum scratch of the flow gradient is allocated here.
+std::tuple<Tensor, Tensor> convex_upsample_backward_impl(const Tensor& gout, const Tensor& flow, const Tensor& mask,
+                                                         std::array<bool, 2> om, bool run) {
+  const char* what = "upsample_flow backward";
+  if (run) check_on_gpu(gout, "grad_out", what), check_on_gpu(flow, "flow", what), check_on_gpu(mask, "mask", what);
+  check_upsample(flow, mask, what);
+  const int64_t b = flow.size(0), h = flow.size(2), w = flow.size(3);
+  TORCH_CHECK(gout.dim() == 4 && gout.size(0) == b && gout.size(1) == 2 && gout.size(2) == 8 * h && gout.size(3) == 8 * w,
+              what, ": grad_out ", gout.sizes(), " must be (B, 2, 8H, 8W) of flow ", flow.sizes());
+  TORCH_CHECK(gout.device() == flow.device(), what, ": grad_out and flow are on different devices");
+  const auto fopt = flow.options().dtype(at::kFloat), mopt = mask.options().dtype(at::kFloat);
+  if (!run)
+    return {at::empty(om[0] ? flow.sizes() : at::IntArrayRef{0}, fopt), at::empty(om[1] ? mask.sizes() : at::IntArrayRef{0}, mopt)};
+  Tensor go = gpu_f32(gout, "grad_out", what), fl = gpu_f32(flow, "flow", what), mk = gpu_f32(mask, "mask", what);
+  Tensor gf = om[0] ? at::empty_like(fl) : at::empty({0}, fopt), gm = om[1] ? at::empty_like(mk) : at::empty({0}, mopt);
+  if (fl.numel() == 0 || (!om[0] && !om[1])) return {gf, gm};
+  c10::hip::HIPGuardMasqueradingAsCUDA g(fl.device());
+  Tensor scratch = om[0] ? at::empty({b, 18, h, w}, fopt) : at::empty({0}, fopt);
+  check_status(oflow_convex_upsample_backward_f32(go.data_ptr<float>(), fl.data_ptr<float>(), mk.data_ptr<float>(), (int)b,
+                                                  (int)h, (int)w, om[0] ? gf.data_ptr<float>() : nullptr,
+                                                  om[1] ? gm.data_ptr<float>() : nullptr,
+                                                  om[0] ? scratch.data_ptr<float>() : nullptr, cur_stream()),
+               what);
+  return {gf, gm};
+}
+std::tuple<Tensor, Tensor> convex_upsample_backward_hip(const Tensor& go, const Tensor& fl, const Tensor& mk,
+                                                        std::array<bool, 2> om) {
+  return convex_upsample_backward_impl(go, fl, mk, om, true);
+}
+std::tuple<Tensor, Tensor> convex_upsample_backward_meta(const Tensor& go, const Tensor& fl, const Tensor& mk,
+                                                         std::array<bool, 2> om) {
+  return convex_upsample_backward_impl(go, fl, mk, om, false);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(oflow, m) {
@@ -744,6 +813,8 @@ TORCH_LIBRARY(oflow, m) {
   m.def("flow_error_stats(Tensor pred, Tensor target, Tensor? valid, float abs_threshold, float rel_threshold, float max_flow, Tensor(a!) accum, bool epe_map) -> Tensor");
   m.def("sequence_loss(Tensor[] flow_preds, Tensor flow_gt, Tensor valid, float[] weights, float max_flow) -> (Tensor, Tensor)");
   m.def("sequence_loss_backward(Tensor grad_out, Tensor[] flow_preds, Tensor flow_gt, Tensor valid, float[] weights, float max_flow, int[] need) -> Tensor[]");
+  m.def("convex_upsample(Tensor flow, Tensor mask) -> Tensor");
+  m.def("convex_upsample_backward(Tensor grad_out, Tensor flow, Tensor mask, bool[2] output_mask) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
@@ -763,6 +834,8 @@ TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
   m.impl("flow_error_stats", &flow_error_stats_hip);
   m.impl("sequence_loss", &sequence_loss_hip);
   m.impl("sequence_loss_backward", &sequence_loss_backward_hip);
+  m.impl("convex_upsample", &convex_upsample_hip);
+  m.impl("convex_upsample_backward", &convex_upsample_backward_hip);
 }
 
 // CPU tensors reach the same kernels, whose first check raises "no CPU fallback" (there is no CPU path)
@@ -783,6 +856,8 @@ TORCH_LIBRARY_IMPL(oflow, CPU, m) {
   m.impl("flow_error_stats", &flow_error_stats_hip);
   m.impl("sequence_loss", &sequence_loss_hip);
   m.impl("sequence_loss_backward", &sequence_loss_backward_hip);
+  m.impl("convex_upsample", &convex_upsample_hip);
+  m.impl("convex_upsample_backward", &convex_upsample_backward_hip);
 }
 
 TORCH_LIBRARY_IMPL(oflow, Meta, m) {
@@ -802,4 +877,6 @@ TORCH_LIBRARY_IMPL(oflow, Meta, m) {
   m.impl("flow_error_stats", &flow_error_stats_meta);
   m.impl("sequence_loss", &sequence_loss_meta);
   m.impl("sequence_loss_backward", &sequence_loss_backward_meta);
+  m.impl("convex_upsample", &convex_upsample_meta);
+  m.impl("convex_upsample_backward", &convex_upsample_backward_meta);
 }

@@ -2,8 +2,9 @@
 
 Same constructor arguments, ``hparams`` attribute, sub-modules and ``state_dict`` keys as the reference's
 LightningModule, so its checkpoints load unchanged. Of the training / evaluation half (`raft.py:149-260`) the metrics
-(``epe_train`` / ``epe_val`` / ``f1_val``), ``validation_step`` and the module-level ``sequence_loss`` are here, on the
-fused reductions of csrc/flow_metrics.hip; the Lightning trainer hooks, optimizers and W&B logging stay out of scope
+(``epe_train`` / ``epe_val`` / ``f1_val``), ``training_step``, ``validation_step`` and the module-level
+``sequence_loss`` are here, on the fused reductions of csrc/flow_metrics.hip and, under autograd, the native backward
+kernels (correlation, convex upsampling, loss); the Lightning trainer hooks, optimizers and W&B logging stay out of scope
 (SURVEY.md §2 row 7). ``forward`` keeps the reference's semantics and return
 values; three output-identical changes remove host work from the loop:
   * the correlation pyramid and every lookup run on the gfx950 kernels (``model.corr.CorrBlock``);
@@ -105,6 +106,7 @@ class RAFT(nn.Module):
         self.epe_train = AverageEndPointError()
         self.epe_val = AverageEndPointError()
         self.f1_val = OutlierRatio(abs_threshold=3.0, rel_threshold=0.05)
+        self.last_train_metrics: Dict[str, float] = {}  # the last training_step's {"1px", "3px", "5px"}
         # plain attributes (not hparams): how GPU inference runs the update block. "split": split-fp16 matrix-core
         # convolutions with fused epilogues (SplitUpdate, default); "fused": MIOpen fp32 convolutions + fused
         # elementwise kernels (FusedUpdate); "module": the nn.Module as written. fused_update=False forces "module".
@@ -112,6 +114,10 @@ class RAFT(nn.Module):
         self.fused_update = True
         # "split": encoders on the split-fp16 kernels (SplitEncoder) in GPU inference; "module": nn.Module (MIOpen)
         self.encoder_impl = "split"
+        # how autograd on the GPU differentiates the convex upsampling: "native": torch.ops.oflow.convex_upsample (the
+        # forward's fused kernel, backward csrc/upsample_backward.hip); "aten": the reference's composition (softmax,
+        # unfold, broadcast product, sum). Without autograd the fused kernel runs either way.
+        self.upsample_impl = "native"
         self.encoder_streams = True  # cnet beside fnet + the corr pyramid (inference, split encoders)
         self.fnet_streams = True  # with encoder_streams: fnet's image0 and image1 halves on two streams
         # split update loop over >= 2 pairs (CorrBlock): the pairs' two halves run on two streams so that one half's
@@ -173,6 +179,20 @@ class RAFT(nn.Module):
             if isinstance(m, nn.BatchNorm2d):
                 m.eval()
 
+    # -- training ----------------------------------------------------------------------------------------
+    def training_step(self, batch: Tuple[Tensor, Tensor, Tensor, Tensor], batch_idx: int = 0) -> Tensor:
+        """One training batch ``(img0, img1, flow_gt, valid)`` (`raft.py:149-175` without Lightning's logging): the
+        forward with ``hparams.iters`` refinements, ``sequence_loss`` with ``hparams.gamma``, ``epe_train`` updated with
+        the last prediction; returns the loss for the caller's ``backward()`` and optimizer. The 1 / 3 / 5 px shares
+        the reference logs are kept on ``last_train_metrics``. On the GPU every step autograd differentiates outside
+        the convolutions is a native kernel: correlation, convex upsampling, sequence loss."""
+        img0, img1, flow, valid = batch
+        flow_predictions = self(img0, img1, iters=self.hparams.iters)
+        loss, metrics = sequence_loss(flow_predictions, flow, valid, gamma=self.hparams.gamma)
+        self.epe_train.update(flow_predictions[-1].detach(), flow, valid)
+        self.last_train_metrics = metrics
+        return loss
+
     # -- evaluation --------------------------------------------------------------------------------------
     def validation_step(self, batch: Tuple[Tensor, Tensor, Tensor, Tensor], batch_idx: int = 0, stage: str = "sintel") -> None:
         """One evaluation batch ``(img0, img1, flow_gt, valid)`` (`raft.py:183-196`): pad for ``stage`` (the reference
@@ -196,10 +216,16 @@ class RAFT(nn.Module):
         return coords0, coords0.clone()
 
     @staticmethod
-    def upsample_flow(flow: Tensor, mask: Tensor) -> Tensor:
-        """[H/8, W/8, 2] -> [H, W, 2] by a softmax-weighted 3x3 convex combination (`raft.py:73-85`)."""
-        if flow.is_cuda and not (torch.is_grad_enabled() and (flow.requires_grad or mask.requires_grad)):
-            return _native.convex_upsample(flow, mask)  # one fused HIP kernel (csrc/upsample.hip)
+    def upsample_flow(flow: Tensor, mask: Tensor, impl: str = "native") -> Tensor:
+        """[H/8, W/8, 2] -> [H, W, 2] by a softmax-weighted 3x3 convex combination (`raft.py:73-85`). On the GPU one
+        fused HIP kernel (csrc/upsample.hip); under autograd the same kernel as ``torch.ops.oflow.convex_upsample``,
+        differentiated by its native transpose (csrc/upsample_backward.hip), unless ``impl`` (the model's
+        ``upsample_impl``) is "aten": then the reference's composition below is what autograd records."""
+        if impl not in ("native", "aten"):
+            raise ValueError(f"upsample_impl must be 'native' or 'aten', got {impl!r}")
+        grad = torch.is_grad_enabled() and (flow.requires_grad or mask.requires_grad)
+        if flow.is_cuda and (not grad or impl == "native"):
+            return _native.convex_upsample(flow, mask)
         n, _, h, w = flow.shape
         mask = torch.softmax(mask.view(n, 1, 9, 8, 8, h, w), dim=2)
         up_flow = F.unfold(8 * flow, [3, 3], padding=1).view(n, 2, 9, 1, 1, h, w)
@@ -466,7 +492,7 @@ class RAFT(nn.Module):
             if up_mask is None:
                 flow_up = upflow8(coords1 - coords0)
             else:
-                flow_up = self.upsample_flow(coords1 - coords0, up_mask)
+                flow_up = self.upsample_flow(coords1 - coords0, up_mask, self.upsample_impl)
             flow_predictions.append(flow_up)
 
         if test_mode:

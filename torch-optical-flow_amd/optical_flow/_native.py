@@ -88,6 +88,7 @@ SYMBOLS = (
     "oflow_flow_error_stats_f32",
     "oflow_sequence_loss_f32",
     "oflow_sequence_loss_backward_f32",
+    "oflow_convex_upsample_backward_f32",
 )
 
 _lib = None
@@ -301,6 +302,8 @@ def load() -> ctypes.CDLL:
     lib.oflow_sequence_loss_f32.argtypes = [PP, I, FP, P, P, I, I, I, I, F, P, P, P, P]
     lib.oflow_sequence_loss_backward_f32.restype = I
     lib.oflow_sequence_loss_backward_f32.argtypes = [P, PP, PP, I, FP, P, P, I, I, I, I, F, P]
+    lib.oflow_convex_upsample_backward_f32.restype = I
+    lib.oflow_convex_upsample_backward_f32.argtypes = [P, P, P, I, I, I, P, P, P, P]
     v = lib.oflow_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liboflow_hip.so ABI version {v}, expected {ABI_VERSION}: rebuild the library")
@@ -488,8 +491,13 @@ def grid_warp(frame: torch.Tensor, flow: torch.Tensor, mode: str, padding_mode: 
 
 def convex_upsample(flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """RAFT.upsample_flow (methods/raft/model/raft.py:73-85): flow (B, 2, H, W), mask (B, 576, H, W) ->
-    (B, 2, 8H, 8W), one fused kernel (softmax over 9 neighbours x unfold(8 * flow) x sum x permute)."""
+    (B, 2, 8H, 8W), one fused kernel (softmax over 9 neighbours x unfold(8 * flow) x sum x permute). When an input
+    needs a gradient the same kernel runs as ``torch.ops.oflow.convex_upsample``, whose autograd formula is the native
+    transpose (csrc/upsample_backward.hip)."""
     what = "upsample_flow"
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (flow, mask)):
+        fl, mk = _tensor(flow, "flow", what), _tensor(mask, "mask", what)
+        return _run(what, fl.device, ops().convex_upsample, fl, mk)  # (the op makes the same checks)
     fl = _gpu_f32(flow, "flow", what)
     mk = _gpu_f32(mask, "mask", what)
     if fl.dim() != 4 or fl.shape[1] != 2 or mk.dim() != 4 or mk.shape[1] != 576 or mk.shape[0] != fl.shape[0] or mk.shape[2:] != fl.shape[2:]:

@@ -17,6 +17,10 @@ Autograd:
     (``sequence_loss_backward``, csrc/flow_metrics.hip); flow_gt and valid get none, and the statistics output is not
     differentiable. ``register_autograd`` handles the ``Tensor[]`` argument (a list of per-prediction gradients, None
     where ``needs_input_grad`` is False).
+  * ``convex_upsample`` (RAFT.upsample_flow): the native transpose (``convex_upsample_backward``,
+    csrc/upsample_backward.hip): one streaming pass recomputes the softmax from the saved flow and mask, writes the mask
+    gradient as whole rows and stages the tap sums of the flow gradient, which a small second kernel gathers in a fixed
+    order (no atomics, deterministic); only the wanted gradients are formed.
 The tiled / NHWC / fp16 on-the-fly lookups are the inference layouts and have no autograd formula; ``flow_error_stats``
 (the metrics' accumulating reduction) has none either.
 """
@@ -46,6 +50,8 @@ OPS = (
     "flow_error_stats",
     "sequence_loss",
     "sequence_loss_backward",
+    "convex_upsample",
+    "convex_upsample_backward",
 )
 _loaded = False
 
@@ -160,6 +166,18 @@ def _seqloss_backward(ctx, grad_loss, _grad_stats):
     return [g.to(p.dtype) if n else None for g, p, n in zip(grads, preds, need)], None, None, None, None
 
 
+def _upsample_setup(ctx, inputs, output):
+    flow, mask = inputs
+    ctx.save_for_backward(flow, mask)  # the softmax is recomputed in the backward: nothing else is kept
+
+
+def _upsample_backward(ctx, grad_out):
+    flow, mask = ctx.saved_tensors
+    need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])]
+    g_flow, g_mask = torch.ops.oflow.convex_upsample_backward(grad_out.contiguous(), flow, mask, need)
+    return (g_flow.to(flow.dtype) if need[0] else None), (g_mask.to(mask.dtype) if need[1] else None)
+
+
 def _register_autograd() -> None:
     reg = torch.library.register_autograd
     reg("oflow::corr_pyramid", _pyramid_backward, setup_context=_pyramid_setup)
@@ -167,3 +185,4 @@ def _register_autograd() -> None:
     reg("oflow::grid_warp", _warp_backward, setup_context=_warp_setup)
     reg("oflow::grid_sample", _sample_backward, setup_context=_sample_setup)
     reg("oflow::sequence_loss", _seqloss_backward, setup_context=_seqloss_setup)
+    reg("oflow::convex_upsample", _upsample_backward, setup_context=_upsample_setup)
