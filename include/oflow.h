@@ -148,6 +148,25 @@ int oflow_corr_lookup_otf_f16(const void* d_f1h, const void* const* d_f2h, const
                               float* d_out, void* stream);
 
 /*
+ * Backward of oflow_corr_lookup_otf_f16 (training with AlternateCorrBlock; csrc/corr_otf_backward.hip). The fp16
+ * roundings of the stored features are taken as identity: the derivative is evaluated at d_f1h / d_f2h as they are.
+ *   d_grad_out    (B, L*(2r+1)^2, H, W) fp32, the gradient of the lookup output (kept in fp32 throughout).
+ *   d_grad_fmap1  (B, C, H, W) fp32 or NULL: gradient of fmap1 (1/sqrt(C) included); every element written once in a
+ *                 fixed order (bit-reproducible).
+ *   d_grad_fmap2  (B, C, H, W) fp32 or NULL: gradient of fmap2 through the floor 2x2 pools; every element written once,
+ *                 from per-level sums formed with fp32 atomic adds (last bits depend on arrival order).
+ *   d_scratch     B*C*sum_l H_l*W_l floats, needed only when d_grad_fmap2 is not NULL (may be NULL otherwise); the call
+ *                 zeroes it itself.
+ * Coordinates get no gradient; queries with NaN / inf / |c / 2^l| >= 2^22 coordinates contribute nothing at level l.
+ * level_h[0] x level_w[0] must be H x W. Same status codes as the forward: radius 0-4, C % 32 == 0, levels >= 2 px.
+ * With both outputs NULL the call checks its arguments and does nothing.
+ */
+int oflow_corr_lookup_otf_backward_f32(const float* d_grad_out, const void* d_f1h, const void* const* d_f2h,
+                                       const int* level_h, const int* level_w, int num_levels, const float* d_coords,
+                                       int B, int C, int H, int W, int radius, float* d_grad_fmap1,
+                                       float* d_grad_fmap2, float* d_scratch, void* stream);
+
+/*
  * Fused elementwise stages of the update block around its (bias-free) MIOpen convolutions
  * (methods/raft/model/update.py:69-161). Tensors are (B, C, P) with contiguous (C, P)
  * parts and an explicit batch stride in floats, so they can be channel slices of concatenated buffers.

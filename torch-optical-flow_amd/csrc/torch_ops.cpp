@@ -13,6 +13,8 @@
 //   corr_lookup_tiled_nhwc(levels, coords, radius, out!) -> ()    same, fp32 NHWC rows (convc1 input)
 //   corr_otf_prepare(fmap1, fmap2, num_levels) -> (Tensor, Tensor[])  AlternateCorrBlock.__init__ (fp16 features)
 //   corr_lookup_otf(f1h, f2h, coords, radius) -> Tensor           AlternateCorrBlock.__call__ (corr.py:90-110)
+//   corr_lookup_alt(fmap1, fmap2, f1h, f2h, coords, radius) -> Tensor   corr_lookup_otf with the fp32 fmaps autograd tracks
+//   corr_lookup_alt_backward(grad_out, f1h, f2h, coords, radius, mask) -> (grad_fmap1, grad_fmap2)   its autograd
 //   grid_warp(frame, flow, mode, padding_mode, align_corners)     optical_flow.warp   (operator.py:8-33)
 //   grid_sample(input, grid, mode, padding_mode, align_corners)   bilinear_sampler    (utils.py:64-80)
 //   corr_lookup_backward(grad_out, coords, radius, H0, W0, L)     transpose of corr_lookup (training, §8(f) row 3)
@@ -321,12 +323,12 @@ Tensor corr_lookup_otf_impl(const Tensor& f1h, const std::vector<Tensor>& f2h, c
     TORCH_CHECK(t.scalar_type() == at::kHalf && t.dim() == 4 && t.size(0) == b && t.size(3) == c && t.is_contiguous(),
                 what, ": fmap2 level ", i, " ", t.sizes(), " must be contiguous fp16 (", b, ", H_l, W_l, ", c, ")");
     TORCH_CHECK(t.device() == coords.device(), what, ": fmap2 level ", i, " and coords are on different devices");
-    ptrs[i] = t.data_ptr();
     hs[i] = (int)t.size(1);
     ws[i] = (int)t.size(2);
   }
   Tensor out = lookup_out(coords, nl, radius);
   if (!run || out.numel() == 0) return out;
+  for (int64_t i = 0; i < nl; ++i) ptrs[i] = f2h[i].data_ptr();  // (fake tensors of a trace have no data pointer)
   Tensor co = gpu_f32(coords, "coords", what);
   c10::hip::HIPGuardMasqueradingAsCUDA g(co.device());
   check_status(oflow_corr_lookup_otf_f16(f1h.data_ptr(), ptrs, hs, ws, (int)nl, co.data_ptr<float>(), (int)b, (int)c,
@@ -340,6 +342,86 @@ Tensor corr_lookup_otf_hip(const Tensor& f1h, const std::vector<Tensor>& f2h, co
 }
 Tensor corr_lookup_otf_meta(const Tensor& f1h, const std::vector<Tensor>& f2h, const Tensor& co, int64_t r) {
   return corr_lookup_otf_impl(f1h, f2h, co, r, false);
+}
+
+// corr_lookup_alt: corr_lookup_otf's forward on (f1h, f2h), with the fp32 feature maps those were prepared from as the
+// arguments autograd tracks (their values are not read: the fp16 roundings count as identity, _ops.py).
+void check_alt_fmaps(const Tensor& fmap1, const Tensor& fmap2, const Tensor& f1h, const char* what) {
+  check_fmaps(fmap1, fmap2, what);
+  TORCH_CHECK(f1h.dim() == 4 && fmap1.size(0) == f1h.size(0) && fmap1.size(1) == f1h.size(3) &&
+                  fmap1.size(2) == f1h.size(1) && fmap1.size(3) == f1h.size(2),
+              what, ": fmap1 ", fmap1.sizes(), " is not the (B, C, H, W) that f1h ", f1h.sizes(), " (B, H, W, C) was prepared from");
+}
+Tensor corr_lookup_alt_hip(const Tensor& fmap1, const Tensor& fmap2, const Tensor& f1h, const std::vector<Tensor>& f2h,
+                           const Tensor& co, int64_t r) {
+  check_alt_fmaps(fmap1, fmap2, f1h, "corr_lookup_alt");
+  return corr_lookup_otf_impl(f1h, f2h, co, r, true);
+}
+Tensor corr_lookup_alt_meta(const Tensor& fmap1, const Tensor& fmap2, const Tensor& f1h, const std::vector<Tensor>& f2h,
+                            const Tensor& co, int64_t r) {
+  check_alt_fmaps(fmap1, fmap2, f1h, "corr_lookup_alt");
+  return corr_lookup_otf_impl(f1h, f2h, co, r, false);
+}
+
+// (grad_fmap1, grad_fmap2) as (B, C, H, W) fp32; an output not wanted is an empty (0-element) tensor and the kernel gets
+// a null pointer for it (no GEMM / no scratch, no atomics). The per-level NHWC scratch of grad_fmap2 is allocated here:
+// B*C*sum_l H_l*W_l floats, nothing that scales with (HW)^2.
+std::tuple<Tensor, Tensor> corr_lookup_alt_backward_impl(const Tensor& gout, const Tensor& f1h, const std::vector<Tensor>& f2h,
+                                                         const Tensor& coords, int64_t radius, std::array<bool, 2> om,
+                                                         bool run) {
+  const char* what = "corr_lookup_alt backward";
+  check_coords(coords, what);
+  if (run) TORCH_CHECK(coords.is_cuda() && gout.is_cuda(), what, ": coords is on ", coords.device(), ", grad_out on ",
+                       gout.device(), "; this MI355X build runs only on ROCm GPU tensors (no CPU fallback)");
+  check_radius(radius, 4, what);
+  const int64_t b = coords.size(0), h = coords.size(2), w = coords.size(3);
+  TORCH_CHECK(f1h.scalar_type() == at::kHalf && f1h.dim() == 4 && f1h.size(0) == b && f1h.size(1) == h &&
+                  f1h.size(2) == w && f1h.is_contiguous(),
+              what, ": f1h ", f1h.sizes(), " must be contiguous fp16 (", b, ", ", h, ", ", w, ", C)");
+  const int64_t c = f1h.size(3), nl = (int64_t)f2h.size();
+  TORCH_CHECK(nl >= 1 && nl <= OFLOW_MAX_LEVELS, what, ": number of pyramid levels ", nl, " outside [1, ",
+              OFLOW_MAX_LEVELS, "]");
+  const int64_t k = 2 * radius + 1;
+  TORCH_CHECK(gout.dim() == 4 && gout.size(0) == b && gout.size(1) == nl * k * k && gout.size(2) == h && gout.size(3) == w,
+              what, ": grad_out ", gout.sizes(), " must be (", b, ", ", nl * k * k, ", ", h, ", ", w, ")");
+  TORCH_CHECK(gout.device() == coords.device() && f1h.device() == coords.device(), what,
+              ": grad_out, f1h and coords are on different devices");
+  const void* ptrs[OFLOW_MAX_LEVELS];
+  int hs[OFLOW_MAX_LEVELS], ws[OFLOW_MAX_LEVELS];
+  int64_t pix = 0;
+  for (int64_t i = 0; i < nl; ++i) {
+    const Tensor& t = f2h[i];
+    TORCH_CHECK(t.scalar_type() == at::kHalf && t.dim() == 4 && t.size(0) == b && t.size(3) == c && t.is_contiguous(),
+                what, ": fmap2 level ", i, " ", t.sizes(), " must be contiguous fp16 (", b, ", H_l, W_l, ", c, ")");
+    TORCH_CHECK(t.device() == coords.device(), what, ": fmap2 level ", i, " and coords are on different devices");
+    hs[i] = (int)t.size(1);
+    ws[i] = (int)t.size(2);
+    pix += t.size(1) * t.size(2);
+  }
+  TORCH_CHECK(hs[0] == h && ws[0] == w, what, ": fmap2 level 0 ", f2h[0].sizes(), " must be (", b, ", ", h, ", ", w, ", C)");
+  const auto opt = coords.options().dtype(at::kFloat);
+  const std::vector<int64_t> full{b, c, h, w}, none{0};
+  Tensor g1 = at::empty(om[0] ? full : none, opt), g2 = at::empty(om[1] ? full : none, opt);
+  if (!run || b * c * h * w == 0 || (!om[0] && !om[1])) return {g1, g2};
+  Tensor go = gpu_f32(gout, "grad_out", what), co = gpu_f32(coords, "coords", what);
+  for (int64_t i = 0; i < nl; ++i) ptrs[i] = f2h[i].data_ptr();
+  c10::hip::HIPGuardMasqueradingAsCUDA g(co.device());
+  Tensor scratch = om[1] ? at::empty({b * c * pix}, opt) : at::empty({0}, opt);
+  check_status(oflow_corr_lookup_otf_backward_f32(go.data_ptr<float>(), f1h.data_ptr(), ptrs, hs, ws, (int)nl,
+                                                  co.data_ptr<float>(), (int)b, (int)c, (int)h, (int)w, (int)radius,
+                                                  om[0] ? g1.data_ptr<float>() : nullptr,
+                                                  om[1] ? g2.data_ptr<float>() : nullptr,
+                                                  om[1] ? scratch.data_ptr<float>() : nullptr, cur_stream()),
+               what);
+  return {g1, g2};
+}
+std::tuple<Tensor, Tensor> corr_lookup_alt_backward_hip(const Tensor& go, const Tensor& f1h, const std::vector<Tensor>& f2h,
+                                                        const Tensor& co, int64_t r, std::array<bool, 2> om) {
+  return corr_lookup_alt_backward_impl(go, f1h, f2h, co, r, om, true);
+}
+std::tuple<Tensor, Tensor> corr_lookup_alt_backward_meta(const Tensor& go, const Tensor& f1h, const std::vector<Tensor>& f2h,
+                                                         const Tensor& co, int64_t r, std::array<bool, 2> om) {
+  return corr_lookup_alt_backward_impl(go, f1h, f2h, co, r, om, false);
 }
 
 // ---------------------------------------------------------------- warp / grid_sample
@@ -804,6 +886,8 @@ TORCH_LIBRARY(oflow, m) {
   m.def("corr_lookup_tiled_nhwc(Tensor[] levels, Tensor coords, int radius, Tensor(a!) out) -> ()");
   m.def("corr_otf_prepare(Tensor fmap1, Tensor fmap2, int num_levels) -> (Tensor, Tensor[])");
   m.def("corr_lookup_otf(Tensor f1h, Tensor[] f2h, Tensor coords, int radius) -> Tensor");
+  m.def("corr_lookup_alt(Tensor fmap1, Tensor fmap2, Tensor f1h, Tensor[] f2h, Tensor coords, int radius) -> Tensor");
+  m.def("corr_lookup_alt_backward(Tensor grad_out, Tensor f1h, Tensor[] f2h, Tensor coords, int radius, bool[2] output_mask) -> (Tensor, Tensor)");
   m.def("grid_warp(Tensor frame, Tensor flow, int mode, int padding_mode, bool align_corners) -> Tensor");
   m.def("grid_sample(Tensor input, Tensor grid, int mode, int padding_mode, bool align_corners) -> Tensor");
   m.def("corr_lookup_backward(Tensor grad_out, Tensor coords, int radius, int H, int W, int num_levels) -> Tensor[]");
@@ -825,6 +909,8 @@ TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
   m.impl("corr_lookup_tiled_nhwc", &corr_lookup_tiled_nhwc_hip);
   m.impl("corr_otf_prepare", &otf_prepare_hip);
   m.impl("corr_lookup_otf", &corr_lookup_otf_hip);
+  m.impl("corr_lookup_alt", &corr_lookup_alt_hip);
+  m.impl("corr_lookup_alt_backward", &corr_lookup_alt_backward_hip);
   m.impl("grid_warp", &grid_warp_hip);
   m.impl("grid_sample", &grid_sample_hip);
   m.impl("corr_lookup_backward", &lookup_backward_hip);
@@ -847,6 +933,8 @@ TORCH_LIBRARY_IMPL(oflow, CPU, m) {
   m.impl("corr_lookup_tiled_nhwc", &corr_lookup_tiled_nhwc_hip);
   m.impl("corr_otf_prepare", &otf_prepare_hip);
   m.impl("corr_lookup_otf", &corr_lookup_otf_hip);
+  m.impl("corr_lookup_alt", &corr_lookup_alt_hip);
+  m.impl("corr_lookup_alt_backward", &corr_lookup_alt_backward_hip);
   m.impl("grid_warp", &grid_warp_hip);
   m.impl("grid_sample", &grid_sample_hip);
   m.impl("corr_lookup_backward", &lookup_backward_hip);
@@ -868,6 +956,8 @@ TORCH_LIBRARY_IMPL(oflow, Meta, m) {
   m.impl("corr_lookup_tiled_nhwc", &corr_lookup_tiled_nhwc_meta);
   m.impl("corr_otf_prepare", &otf_prepare_meta);
   m.impl("corr_lookup_otf", &corr_lookup_otf_meta);
+  m.impl("corr_lookup_alt", &corr_lookup_alt_meta);
+  m.impl("corr_lookup_alt_backward", &corr_lookup_alt_backward_meta);
   m.impl("grid_warp", &grid_warp_meta);
   m.impl("grid_sample", &grid_sample_meta);
   m.impl("corr_lookup_backward", &lookup_backward_meta);

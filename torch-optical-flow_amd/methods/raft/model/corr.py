@@ -109,14 +109,25 @@ class AlternateCorrBlock:
     equals the dense pyramid by linearity of the pooling (`corr.py:38-54, 79-87`). Features are stored as NHWC
     fp16 and multiplied on v_mfma_f32_16x16x32_f16 with fp32 accumulation (BASELINE configs[4]: 1080p, fp16);
     outputs are fp32 like ``CorrBlock`` (Q5). Holds O(B*C*H*W) memory instead of O(B*(H*W)^2).
+
+    Under autograd (either feature map requires grad) the fp16 copies are prepared from the detached maps and the
+    lookups run as ``torch.ops.oflow.corr_lookup_alt``: the same forward, bit for bit, whose native backward
+    (csrc/corr_otf_backward.hip) returns fp32 gradients for the feature maps with the fp16 roundings taken as identity
+    -- so training needs no volume either. Coordinates get no gradient, as in the reference.
     """
 
     def __init__(self, fmap1: Tensor, fmap2: Tensor, num_levels: int = 4, radius: int = 4) -> None:
         self.num_levels = num_levels
         self.radius = radius
+        self._fmaps = None
+        if torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad):
+            self._fmaps = (fmap1, fmap2)
+            fmap1, fmap2 = fmap1.detach(), fmap2.detach()
         self.fmap1_f16, self.fmap2_pyramid_f16 = _native.otf_prepare(fmap1, fmap2, num_levels)
 
     def __call__(self, coords: Tensor) -> Tensor:
+        if self._fmaps is not None and torch.is_grad_enabled():
+            return _native.corr_lookup_alt(*self._fmaps, self.fmap1_f16, self.fmap2_pyramid_f16, coords, self.radius)
         return _native.corr_lookup_otf(self.fmap1_f16, self.fmap2_pyramid_f16, coords, self.radius)
 
     def lookup_nhwc(self, coords: Tensor, out: Tensor) -> Tensor:

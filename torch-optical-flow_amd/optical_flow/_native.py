@@ -89,6 +89,7 @@ SYMBOLS = (
     "oflow_sequence_loss_f32",
     "oflow_sequence_loss_backward_f32",
     "oflow_convex_upsample_backward_f32",
+    "oflow_corr_lookup_otf_backward_f32",
 )
 
 _lib = None
@@ -304,6 +305,8 @@ def load() -> ctypes.CDLL:
     lib.oflow_sequence_loss_backward_f32.argtypes = [P, PP, PP, I, FP, P, P, I, I, I, I, F, P]
     lib.oflow_convex_upsample_backward_f32.restype = I
     lib.oflow_convex_upsample_backward_f32.argtypes = [P, P, P, I, I, I, P, P, P, P]
+    lib.oflow_corr_lookup_otf_backward_f32.restype = I
+    lib.oflow_corr_lookup_otf_backward_f32.argtypes = [P, P, PP, IP, IP, I, P, I, I, I, I, I, P, P, P, P]
     v = lib.oflow_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liboflow_hip.so ABI version {v}, expected {ABI_VERSION}: rebuild the library")
@@ -596,6 +599,15 @@ def corr_lookup_otf(f1h: torch.Tensor, f2h: Sequence[torch.Tensor], coords: torc
     co = _tensor(coords, "coords", "corr_lookup_otf")
     _no_grad_input(co, "coords", "corr_lookup_otf")
     return _run("corr_lookup_otf", co.device, ops().corr_lookup_otf, f1h, list(f2h), co, int(radius))
+
+
+def corr_lookup_alt(fmap1: torch.Tensor, fmap2: torch.Tensor, f1h: torch.Tensor, f2h: Sequence[torch.Tensor],
+                    coords: torch.Tensor, radius: int) -> torch.Tensor:
+    """``corr_lookup_otf`` on (f1h, f2h), differentiable in the fp32 feature maps they were prepared from
+    (``torch.ops.oflow.corr_lookup_alt``: the native backward of csrc/corr_otf_backward.hip, the fp16 roundings taken
+    as identity); coords get no gradient, as in the reference."""
+    co = _tensor(coords, "coords", "corr_lookup_alt")
+    return _run("corr_lookup_otf", co.device, ops().corr_lookup_alt, fmap1, fmap2, f1h, list(f2h), co.detach(), int(radius))
 
 
 ACT = {"none": 0, "relu": 1, "sigmoid": 2, "tanh": 3}

@@ -21,8 +21,14 @@ Autograd:
     csrc/upsample_backward.hip): one streaming pass recomputes the softmax from the saved flow and mask, writes the mask
     gradient as whole rows and stages the tap sums of the flow gradient, which a small second kernel gathers in a fixed
     order (no atomics, deterministic); only the wanted gradients are formed.
-The tiled / NHWC / fp16 on-the-fly lookups are the inference layouts and have no autograd formula; ``flow_error_stats``
-(the metrics' accumulating reduction) has none either.
+  * ``corr_lookup_alt`` (AlternateCorrBlock under autograd): ``corr_lookup_otf``'s forward on the fp16 features, with
+    the fp32 feature maps they were prepared from as the tracked arguments. The fp16 roundings count as identity; the
+    native transpose (``corr_lookup_alt_backward``, csrc/corr_otf_backward.hip) evaluates the derivative at the stored
+    fp16 values with the gradients kept in fp32 (fp32 MFMA). Only f1h, f2h and coords are saved: nothing that scales with
+    (HW)^2 exists in either direction. grad_fmap1 is written in a fixed order (bit-reproducible); grad_fmap2 sums
+    overlapping windows with fp32 atomics (last bits vary from run to run). coords get no gradient.
+The tiled / NHWC lookups and the raw fp16 on-the-fly ops (``corr_otf_prepare`` / ``corr_lookup_otf``) are the inference
+layouts and have no autograd formula; ``flow_error_stats`` (the metrics' accumulating reduction) has none either.
 """
 from __future__ import annotations
 
@@ -52,6 +58,8 @@ OPS = (
     "sequence_loss_backward",
     "convex_upsample",
     "convex_upsample_backward",
+    "corr_lookup_alt",
+    "corr_lookup_alt_backward",
 )
 _loaded = False
 
@@ -178,6 +186,22 @@ def _upsample_backward(ctx, grad_out):
     return (g_flow.to(flow.dtype) if need[0] else None), (g_mask.to(mask.dtype) if need[1] else None)
 
 
+def _alt_setup(ctx, inputs, output):
+    _fmap1, _fmap2, f1h, f2h, coords, radius = inputs
+    ctx.save_for_backward(f1h, coords, *f2h)  # O(B*C*H*W): the fp32 fmaps are not kept, no volume exists
+    ctx.radius = radius
+    ctx.dtypes = (_fmap1.dtype, _fmap2.dtype)
+
+
+def _alt_backward(ctx, grad_out):
+    f1h, coords, *f2h = ctx.saved_tensors
+    need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])]
+    g1, g2 = torch.ops.oflow.corr_lookup_alt_backward(grad_out.contiguous(), f1h, f2h, coords, ctx.radius, need)
+    d1, d2 = ctx.dtypes  # fp32 in AlternateCorrBlock: the casts are no-ops there
+    # (a Tensor[] argument takes a list of its own length)
+    return (g1.to(d1) if need[0] else None), (g2.to(d2) if need[1] else None), None, [None] * len(f2h), None, None
+
+
 def _register_autograd() -> None:
     reg = torch.library.register_autograd
     reg("oflow::corr_pyramid", _pyramid_backward, setup_context=_pyramid_setup)
@@ -186,3 +210,4 @@ def _register_autograd() -> None:
     reg("oflow::grid_sample", _sample_backward, setup_context=_sample_setup)
     reg("oflow::sequence_loss", _seqloss_backward, setup_context=_seqloss_setup)
     reg("oflow::convex_upsample", _upsample_backward, setup_context=_upsample_setup)
+    reg("oflow::corr_lookup_alt", _alt_backward, setup_context=_alt_setup)
