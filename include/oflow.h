@@ -26,6 +26,8 @@
  *                              + optical_flow/metrics/f1.py:34-55 (OutlierRatio.update)
  *   oflow_sequence_loss_f32, oflow_sequence_loss_backward_f32 <- methods/raft/model/raft.py:231-260 (sequence_loss
  *                              and its autograd)
+ *   oflow_forward_interpolate_f32 <- nothing in the reference: it produces the flow_init that
+ *                              methods/raft/model/raft.py:122-123 consumes (upstream RAFT's forward_interpolate)
  */
 #ifndef OFLOW_H_
 #define OFLOW_H_
@@ -564,6 +566,23 @@ int oflow_sequence_loss_f32(const float* const* d_preds, int n_preds, const floa
 int oflow_sequence_loss_backward_f32(const float* d_grad_out, const float* const* d_preds, float* const* d_grads,
                                      int n_preds, const float* weights, const float* d_flow_gt, const void* d_valid,
                                      int valid_kind, int B, int H, int W, float max_flow, void* stream);
+
+/*
+ * Warm-start initialiser (RAFT's video mode; csrc/forward_interpolate.hip): the flow of one pair, forward-projected
+ * along itself, as `flow_init` of the next pair -- upstream RAFT's forward_interpolate (scipy griddata(method="nearest")
+ * on float64 coordinates) with the tie-break made explicit, on the device. The reference has no such function;
+ * it only consumes the result (methods/raft/model/raft.py:122-123).
+ * oflow_forward_interpolate_f32: d_flow, d_out contiguous (B, 2, H, W) fp32, channel 0 = dx, 1 = dy; d_out must not
+ *   alias d_flow. Per image, with all selection arithmetic in float64:
+ *     source s = y*W + x lands at x1 = x + (double)dx[s], y1 = y + (double)dy[s] (exact) and is LANDED iff
+ *     x1 > 0 && x1 < W && y1 > 0 && y1 < H (so a NaN or +-inf flow never lands);
+ *     out[:, qy, qx] = flow[:, s*], s* the landed source with the least (qx - x1)^2 + (qy - y1)^2 (two products and
+ *     one sum, each rounded once to float64, no FMA contraction), ties to the LOWEST s; the selected fp32 values are
+ *     copied unchanged; an image with no landed source gives all zeros (a cold start).
+ *   Images are independent; no atomics and a fixed reduction order: bit-identical from run to run. One launch, no
+ *   scratch, O((H*W)^2) candidate evaluations per image. B <= 65535, H*W <= 2^30.
+ */
+int oflow_forward_interpolate_f32(const float* d_flow, int B, int H, int W, float* d_out, void* stream);
 
 #ifdef __cplusplus
 }

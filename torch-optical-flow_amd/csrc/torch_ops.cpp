@@ -26,6 +26,7 @@
 //   sequence_loss_backward(grad_out, flow_preds, flow_gt, valid, weights, max_flow, need) -> Tensor[]   its autograd
 //   convex_upsample(flow, mask) -> Tensor                                                   RAFT.upsample_flow (raft.py:73-85)
 //   convex_upsample_backward(grad_out, flow, mask, mask2) -> (grad_flow, grad_mask)         its autograd
+//   forward_interpolate(flow) -> Tensor                           warm-start flow_init (upstream RAFT's forward_interpolate)
 #include <array>
 #include <torch/library.h>
 #include <ATen/ATen.h>
@@ -876,6 +877,28 @@ std::tuple<Tensor, Tensor> convex_upsample_backward_meta(const Tensor& go, const
   return convex_upsample_backward_impl(go, fl, mk, om, false);
 }
 
+// ---------------------------------------------------------------- warm start (forward_interpolate.hip)
+Tensor forward_interpolate_impl(const Tensor& flow, bool run) {
+  const char* what = "forward_interpolate";
+  if (run) check_on_gpu(flow, "flow", what);
+  TORCH_CHECK(flow.dim() == 4 && flow.size(1) == 2, what, ": flow must be (B, 2, H, W), got ", flow.sizes());
+  TORCH_CHECK(flow.scalar_type() == at::kFloat, what, ": flow must be float32, got ", flow.scalar_type());
+  const int64_t b = flow.size(0), h = flow.size(2), w = flow.size(3);
+  TORCH_CHECK(b <= 65535 && h * w <= (int64_t(1) << 30), what, ": flow ", flow.sizes(),
+              " is past the kernel's grid (B <= 65535, H*W <= 2^30)");
+  if (!run) return at::empty(flow.sizes(), flow.options());
+  Tensor fl = flow.contiguous();
+  Tensor out = at::empty(fl.sizes(), fl.options());
+  if (out.numel() == 0) return out;
+  c10::hip::HIPGuardMasqueradingAsCUDA g(fl.device());
+  check_status(oflow_forward_interpolate_f32(fl.data_ptr<float>(), (int)b, (int)h, (int)w, out.data_ptr<float>(),
+                                             cur_stream()),
+               what);
+  return out;
+}
+Tensor forward_interpolate_hip(const Tensor& flow) { return forward_interpolate_impl(flow, true); }
+Tensor forward_interpolate_meta(const Tensor& flow) { return forward_interpolate_impl(flow, false); }
+
 }  // namespace
 
 TORCH_LIBRARY(oflow, m) {
@@ -899,6 +922,7 @@ TORCH_LIBRARY(oflow, m) {
   m.def("sequence_loss_backward(Tensor grad_out, Tensor[] flow_preds, Tensor flow_gt, Tensor valid, float[] weights, float max_flow, int[] need) -> Tensor[]");
   m.def("convex_upsample(Tensor flow, Tensor mask) -> Tensor");
   m.def("convex_upsample_backward(Tensor grad_out, Tensor flow, Tensor mask, bool[2] output_mask) -> (Tensor, Tensor)");
+  m.def("forward_interpolate(Tensor flow) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
@@ -922,6 +946,7 @@ TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
   m.impl("sequence_loss_backward", &sequence_loss_backward_hip);
   m.impl("convex_upsample", &convex_upsample_hip);
   m.impl("convex_upsample_backward", &convex_upsample_backward_hip);
+  m.impl("forward_interpolate", &forward_interpolate_hip);
 }
 
 // CPU tensors reach the same kernels, whose first check raises "no CPU fallback" (there is no CPU path)
@@ -946,6 +971,7 @@ TORCH_LIBRARY_IMPL(oflow, CPU, m) {
   m.impl("sequence_loss_backward", &sequence_loss_backward_hip);
   m.impl("convex_upsample", &convex_upsample_hip);
   m.impl("convex_upsample_backward", &convex_upsample_backward_hip);
+  m.impl("forward_interpolate", &forward_interpolate_hip);
 }
 
 TORCH_LIBRARY_IMPL(oflow, Meta, m) {
@@ -969,4 +995,5 @@ TORCH_LIBRARY_IMPL(oflow, Meta, m) {
   m.impl("sequence_loss_backward", &sequence_loss_backward_meta);
   m.impl("convex_upsample", &convex_upsample_meta);
   m.impl("convex_upsample_backward", &convex_upsample_backward_meta);
+  m.impl("forward_interpolate", &forward_interpolate_meta);
 }

@@ -14,6 +14,7 @@ except ImportError:  # pragma: no cover - path bootstrap
 
 from .corr import AlternateCorrBlock, CorrBlock  # noqa: E402
 from .raft import RAFT  # noqa: E402
-from .utils import InputPadder, bilinear_sampler, coords_grid, upflow8  # noqa: E402
+from .utils import InputPadder, bilinear_sampler, coords_grid, forward_interpolate, upflow8  # noqa: E402
 
-__all__ = ["RAFT", "AlternateCorrBlock", "CorrBlock", "InputPadder", "bilinear_sampler", "coords_grid", "upflow8"]
+__all__ = ["RAFT", "AlternateCorrBlock", "CorrBlock", "InputPadder", "bilinear_sampler", "coords_grid",
+           "forward_interpolate", "upflow8"]

@@ -334,7 +334,11 @@ class RAFT(nn.Module):
     ) -> Union[Tensor, Tuple[Tensor, Tensor], List[Tensor]]:
         """Estimate optical flow between pairs of frames (`raft.py:87-147`). Images (B, 3, H, W) in [0, 255]
         with H, W divisible by 8 (use ``InputPadder``). Returns ``(coords1 - coords0, flow_up)`` in test mode,
-        else the list of ``iters`` upsampled predictions. On the GPU in inference the split-fp16 range guard
+        else the list of ``iters`` upsampled predictions. ``flow_init`` (B, 2, H/8, W/8), added to the initial
+        coordinates (`raft.py:122-123`), is the warm start of RAFT's video mode: pass
+        ``model.forward_interpolate(low)``, where ``low`` is the first value the test-mode forward of the previous
+        pair of the sequence returned; ``None`` starts cold (``predict.py --warm_start`` runs a folder this way).
+        On the GPU in inference the split-fp16 range guard
         (``range_guard``) reports an operand that left the fp16 range with RuntimeError: "sync" raises from this
         forward; "deferred" (default) does not wait -- this forward's status is ``last_range_snapshot``
         (``.overflowed()`` waits for it), and a later forward or ``check_range()`` raises for it."""

@@ -11,6 +11,10 @@ bytes that are written into pinned host memory, and a writer thread waits on tha
 files while the GPU already runs the next pair. Differences from the reference: no jsonargparse/torchvision
 (argparse and a 20-line grid writer instead), ``ext`` results are sorted like the unfiltered listing (the
 reference keeps an un-indexable glob there), and ``checkpoint=None`` uses the deterministic synthetic weights.
+
+``warm_start`` (off by default; an addition, RAFT's video mode): the folder is treated as ONE sequence, and every pair
+after the first starts from the previous pair's low-resolution flow projected forward along itself
+(``model.forward_interpolate`` -> ``flow_init``), on the device on the model's stream, with no host sync added.
 """
 from __future__ import annotations
 
@@ -29,7 +33,7 @@ from torch.utils.data import DataLoader, Dataset
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from model import RAFT, synthetic  # noqa: E402
-from model.utils import InputPadder  # noqa: E402
+from model.utils import InputPadder, forward_interpolate  # noqa: E402
 
 import optical_flow  # noqa: E402
 from optical_flow import _native  # noqa: E402
@@ -96,10 +100,14 @@ def main(
     visualize: bool = True,
     eval_mode: bool = False,
     num_workers: int = 4,
+    warm_start: bool = False,
 ) -> int:
     """Predict flow for every consecutive pair in ``source`` and write it to ``destination`` (predict.py:39-95).
     ``eval_mode`` puts the model in eval mode; the reference never calls ``.eval()`` (cnet's batch norm then uses
     batch statistics), which stays the default. ``num_workers`` image-decoding processes (the reference's 4).
+    ``warm_start`` treats the folder as one sequence: each pair's low-resolution flow, forward-interpolated on the
+    device, initialises the next pair (``flow_init``); the first pair, and a pair whose padded size differs from the
+    previous one's, starts cold. Off (the default), every pair starts cold, as in the reference.
     Returns the number of pairs written."""
     if iters <= 0:
         raise ValueError("iters must be a positive integer")
@@ -124,13 +132,19 @@ def main(
     # and re-raises a failed write at the next pair instead of after the whole folder
     slots = [None] * WRITES_IN_FLIGHT
     count = 0
+    prev_low = None  # warm start: the previous pair's 1/8-resolution flow (B, 2, H/8, W/8), on the device
     with torch.inference_mode(), ThreadPoolExecutor(max_workers=1) as writer:
         for i, (img0, img1) in enumerate(loader):
             img0 = img0.to(device, non_blocking=True)
             img1 = img1.to(device, non_blocking=True)
             padder = InputPadder(img0.shape)
             padded0, padded1 = padder.pad(img0, img1)
-            _, flow = model(padded0, padded1, iters=iters, test_mode=True)
+            flow_init = None
+            if prev_low is not None and prev_low.shape[-2:] == (padded0.shape[-2] // 8, padded0.shape[-1] // 8):
+                flow_init = forward_interpolate(prev_low)  # one kernel on the model's stream, no sync
+            low, flow = model(padded0, padded1, iters=iters, flow_init=flow_init, test_mode=True)
+            if warm_start:
+                prev_low = low
             snap = model.last_range_snapshot  # this pair's own range status, checked by the writer before writing
             assert flow.shape[0] == 1
             flow = padder.unpad(flow)[0]
@@ -183,8 +197,11 @@ def _cli(argv=None) -> int:
     ap.add_argument("--visualize", type=lambda s: s.lower() in ("1", "true", "yes"), default=True)
     ap.add_argument("--eval_mode", action="store_true")
     ap.add_argument("--num_workers", type=int, default=4)
+    ap.add_argument("--warm_start", action="store_true",
+                    help="treat the folder as one sequence: initialise each pair from the previous pair's flow")
     a = ap.parse_args(argv)
-    main(a.source, a.destination, a.checkpoint, a.ext, a.overwrite, a.iters, a.visualize, a.eval_mode, a.num_workers)
+    main(a.source, a.destination, a.checkpoint, a.ext, a.overwrite, a.iters, a.visualize, a.eval_mode, a.num_workers,
+         a.warm_start)
     return 0
 
 

@@ -90,6 +90,7 @@ SYMBOLS = (
     "oflow_sequence_loss_backward_f32",
     "oflow_convex_upsample_backward_f32",
     "oflow_corr_lookup_otf_backward_f32",
+    "oflow_forward_interpolate_f32",
 )
 
 _lib = None
@@ -307,6 +308,8 @@ def load() -> ctypes.CDLL:
     lib.oflow_convex_upsample_backward_f32.argtypes = [P, P, P, I, I, I, P, P, P, P]
     lib.oflow_corr_lookup_otf_backward_f32.restype = I
     lib.oflow_corr_lookup_otf_backward_f32.argtypes = [P, P, PP, IP, IP, I, P, I, I, I, I, I, P, P, P, P]
+    lib.oflow_forward_interpolate_f32.restype = I
+    lib.oflow_forward_interpolate_f32.argtypes = [P, I, I, I, P, P]
     v = lib.oflow_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liboflow_hip.so ABI version {v}, expected {ABI_VERSION}: rebuild the library")
@@ -514,6 +517,14 @@ def convex_upsample(flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     with torch.cuda.device(fl.device), _Timed("upsample_flow", fl.device):
         _check(load().oflow_convex_upsample_f32(fl.data_ptr(), mk.data_ptr(), b, h, w, out.data_ptr(), _stream(fl.device)), what)
     return out
+
+
+def forward_interpolate(flow: torch.Tensor) -> torch.Tensor:
+    """The warm-start initialiser of a (B, 2, H, W) fp32 flow (``torch.ops.oflow.forward_interpolate``, include/oflow.h
+    oflow_forward_interpolate_f32): every pixel takes the flow of the source pixel that lands nearest to it, selected in
+    float64, ties to the lowest source index, zeros when nothing lands. No autograd formula: the input is detached."""
+    fl = _tensor(flow, "flow", "forward_interpolate")
+    return _run("forward_interpolate", fl.device, ops().forward_interpolate, fl.detach())
 
 
 FLOW2RGB_METHODS = {"baker": 0, "hsv": 1, "meister": 2}

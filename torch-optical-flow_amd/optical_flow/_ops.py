@@ -28,7 +28,9 @@ Autograd:
     (HW)^2 exists in either direction. grad_fmap1 is written in a fixed order (bit-reproducible); grad_fmap2 sums
     overlapping windows with fp32 atomics (last bits vary from run to run). coords get no gradient.
 The tiled / NHWC lookups and the raw fp16 on-the-fly ops (``corr_otf_prepare`` / ``corr_lookup_otf``) are the inference
-layouts and have no autograd formula; ``flow_error_stats`` (the metrics' accumulating reduction) has none either.
+layouts and have no autograd formula; ``flow_error_stats`` (the metrics' accumulating reduction) has none either, nor
+has ``forward_interpolate`` (the warm-start initialiser, csrc/forward_interpolate.hip: a nearest-landed-source selection
+in float64, piecewise constant in its input; callers detach the input, ``model.utils.forward_interpolate``).
 """
 from __future__ import annotations
 
@@ -60,6 +62,7 @@ OPS = (
     "convex_upsample_backward",
     "corr_lookup_alt",
     "corr_lookup_alt_backward",
+    "forward_interpolate",
 )
 _loaded = False
 
