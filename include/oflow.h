@@ -17,7 +17,7 @@
  *                              + methods/raft/model/utils.py:64-80 (bilinear_sampler)
  *   oflow_grid_warp_f32     <- optical_flow/operator/operator.py:8-56 (warp, warp_grid -> F.grid_sample)
  *   oflow_conv_s32 & co.    <- methods/raft/model/update.py:40-161 (update-block convolutions)
- *   oflow_stem_patches_s32, oflow_norm_*, oflow_conv_s32_ex <- methods/raft/model/extractor.py:35-231 (encoders)
+ *   oflow_stem_patches_s32, oflow_norm_*, oflow_conv_s32 <- methods/raft/model/extractor.py:35-231 (encoders)
  *   oflow_convex_upsample_f32 <- methods/raft/model/raft.py:73-85 (RAFT.upsample_flow)
  *   oflow_convex_upsample_backward_f32 <- the same lines under autograd (the training step, raft.py:149-175)
  *   oflow_flow_stats_f32, oflow_flow2rgb_f32 <- optical_flow/visualization/flow2rgb.py:19-73 (+ visualization/methods/)
@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define OFLOW_ABI_VERSION 1
+#define OFLOW_ABI_VERSION 2
 
 #define OFLOW_OK 0
 #define OFLOW_E_NULL (-1)      /* a required pointer is NULL */
@@ -58,13 +58,13 @@ extern "C" {
 #define OFLOW_PAD_BORDER 1
 #define OFLOW_PAD_REFLECTION 2
 
-/* oflow_conv_s32_ex2 input formats */
+/* oflow_conv_s32_desc.in_format */
 #define OFLOW_IN_S32 0
 #define OFLOW_IN_F32_NORM 1
 #define OFLOW_IN_F32 2
 #define OFLOW_IN_IMG7S2 3
 #define OFLOW_IN_FLOW7 4
-/* oflow_conv_s32_ex6: the flow-head epilogue (epilogues 0-2: oflow_conv_s32) */
+/* oflow_conv_s32_desc.epilogue: the flow-head epilogue (epilogues 0-2: plain numbers) */
 #define OFLOW_EPI_FLOW_HEAD 3
 
 int oflow_abi_version(void);
@@ -193,17 +193,7 @@ int oflow_gru_blend_f32(const float* d_zr, long long szr, const float* d_bz, con
  * 22 significant bits). A channel slice starting at group g0 is (base + g0*128, pixel stride G*128).
  * Padding channels (beyond the real ones, up to a multiple of 32) must hold zeros.
  *
- * oflow_conv_s32: stride-1 'same' convolution, kernel kh x kw in {1x1, 3x3, 1x5, 5x1}, over in_groups*32 input
- *   channels. d_wpack = weights packed as [in_groups][kh*kw][n_pad][hi[32] | lo[32]] fp16 after scaling output
- *   channel n by 2^s_n (|w| <= 2^14); d_wscale[n] = 2^-s_n. block_n in {32, 64, 128} divides n_pad.
- *   value = act(acc * wscale[n] + bias[n]) * out_scale, act 0 none, 1 relu, 2 sigmoid, 3 tanh, then
- *   epilogue 0: stored to S32 d_y0 (and d_y1 if not NULL) for channels n < N, and/or to fp32 NCHW d_f32
- *               (batch / channel strides in floats; f32_accumulate = 1 adds to it);
- *   epilogue 1 (GRU gates, N = 2*CH): n < CH -> z = sigmoid(.) into d_gru_z ([P][CH] fp32);
- *               n >= CH -> sigmoid(.) * d_gru_h[p][n-CH] into S32 d_y0 channel n-CH   (update.py:91-96)
- *   epilogue 2 (GRU candidate, N = CH): h = (1 - z) * h + z * tanh(.), in place in d_gru_h and into S32 d_y0
- *               (update.py:96-97). (act is ignored by epilogues 1 and 2.) Epilogues 1 and 2 read / write d_gru_h
- *               and d_gru_z as 16-B vectors: both must be 16-byte aligned (else OFLOW_E_ALIGN).
+ * oflow_conv_s32: the convolution itself; see its descriptor, oflow_conv_s32_desc, below.
  * oflow_pack_s32_f32: d_x (B, C, H, W) fp32 with batch stride x_batch_stride -> act -> S32 d_y0 (and d_y1) channels
  *   dst_channel + c (dst_channel % 8 == 0; the last 8-channel chunk is zero-filled past C), and optionally a
  *   [P][nhwc_pixel_stride] fp32 copy.                                     (raft.py:115-118: tanh / relu of cnet)
@@ -211,16 +201,135 @@ int oflow_gru_blend_f32(const float* d_zr, long long szr, const float* d_bz, con
  *   (d_patches: S32 with 4 groups; channel t*2 + c = flow c at tap t = ky*7 + kx, zero padded) and, if not NULL,
  *   the 2 flow channels at d_flow0 / d_flow1 (byte address of the hi half of the x channel; y follows).
  */
-int oflow_conv_s32(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack, int n_pad,
-                   const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh, int kw, int block_n,
-                   int epilogue, int activation, float out_scale, void* d_y0, long long y0_pixel_stride, void* d_y1,
-                   long long y1_pixel_stride, float* d_f32, long long f32_batch_stride, long long f32_channel_stride,
-                   int f32_accumulate, float* d_gru_h, float* d_gru_z, int gru_channels, void* stream);
 int oflow_pack_s32_f32(const float* d_x, long long x_batch_stride, int C, int B, int H, int W, int activation,
                        int dst_channel, void* d_y0, long long y0_pixel_stride, void* d_y1, long long y1_pixel_stride,
                        float* d_nhwc, int nhwc_pixel_stride, void* stream);
 int oflow_flow_prep_s32(const float* d_coords, int B, int H, int W, void* d_patches, void* d_flow0,
                         long long flow0_pixel_stride, void* d_flow1, long long flow1_pixel_stride, void* stream);
+
+/*
+ * oflow_conv_s32: the split-fp16 convolution of the update block (update.py:40-161) and the encoders
+ * (extractor.py:35-231), described by one oflow_conv_s32_desc. A zero-filled descriptor has every optional feature off
+ * (S32 input, epilogue 0, no activation, every optional pointer NULL); the caller sets struct_size =
+ * sizeof(oflow_conv_s32_desc) and the fields it needs. A stride, count or flag that belongs to a NULL pointer is
+ * ignored. desc NULL: OFLOW_E_NULL; struct_size != sizeof(oflow_conv_s32_desc): OFLOW_E_MODE, before any other field
+ * is read (a caller built against another layout of this struct).
+ */
+typedef struct oflow_conv_s32_desc {
+  unsigned int struct_size;
+  /* Input: OFLOW_IN_S32, d_x an S32 slice of in_groups groups (16-B aligned, x_pixel_stride % 128 == 0). The other
+   * formats split fp32 values into hi + lo while the kernel stages them (epilogue 0 only):
+   *   OFLOW_IN_F32_NORM: the raw fp32 NHWC output [P][in_groups*32] of the previous convolution (x_pixel_stride =
+   *     in_groups*128), normalised and ReLU'd while staged, x = max(0, raw * d_in_scale[b, c] + d_in_shift[b, c])
+   *     ([B][in_groups*32] each) -- the instance norm + ReLU between a residual block's two 3x3 convs
+   *     (extractor.py:75-76) never materialises (3x3, in_groups <= 4);
+   *   OFLOW_IN_F32: an fp32 NHWC input of cin = x_pixel_stride/4 channels per pixel ((in_groups-1)*32 < cin <=
+   *     in_groups*32, x_pixel_stride % 16 == 0; channels past cin stage as zeros) (1x1, block_n 128: convc1 reading
+   *     oflow_corr_lookup_tiled_nhwc_f32's rows);
+   *   OFLOW_IN_IMG7S2: the encoders' stem (extractor.py:186, 7x7 / stride 2 / pad 3 on a 3-channel image) straight from
+   *     the fp32 NCHW image d_x (B, 3, 2H, 2W) for an output of H x W (x_pixel_stride ignored): each output tile builds
+   *     its patch-matrix operand (channel t*3 + c, t = ky*7 + kx; in_groups 5, weights packed as for
+   *     oflow_stem_patches_s32's matrix) from an LDS window, so no patch matrix is written (1x1 geometry, block_n 64);
+   *   OFLOW_IN_FLOW7: the motion encoder's convf1 (update.py:116, 7x7 / pad 3 on the 2-channel flow) straight from
+   *     coords1 d_x (B, 2, H, W) fp32 (x_pixel_stride ignored): flow = coords1 - the pixel grid (raft.py:129) and its
+   *     patch operand (channel t*2 + c; in_groups 4, weights packed as for oflow_flow_prep_s32's matrix) are built per
+   *     output tile: bit for bit the conv of that matrix, which is then not written (1x1 geometry, block_n 128). */
+  int in_format, in_groups;
+  const void* d_x;
+  long long x_pixel_stride;
+  const float *d_in_scale, *d_in_shift;
+  /* Weights: d_wpack = [in_groups][kh*kw][n_pad][hi[32] | lo[32]] fp16 after scaling output channel n by 2^s_n
+   * (|w| <= 2^14), 16-B aligned; d_wscale[n] = 2^-s_n ([n_pad]); d_bias [N] or NULL; N real output channels.
+   * d_wfrag: an optional fragment-major copy of d_wpack (same bytes, reordered [group][tap][n/32][slice][hi|lo][k half]
+   * [row][8]: one wave's 32x16 MFMA B fragment is 1 KB contiguous and goes straight into registers, skipping the LDS
+   * staging of B; 16-B aligned, n_pad % 32 == 0). Used, on S32 input without d_stats outside the small-grid tiles, by
+   * every multi-tap convolution with block_n 128 and by 3x3 convolutions with block_n 64 or 32 (these two measured
+   * slower in the RAFT step, DESIGN.md §4 r04: pass NULL for them unless comparing); other shapes ignore it. */
+  const void *d_wpack, *d_wfrag;
+  const float *d_wscale, *d_bias;
+  int n_pad, N;
+  /* Geometry: a stride-1 'same' convolution of B images of H x W pixels, kernel kh x kw in {1x1, 3x3, 1x5, 5x1} or 2x2
+   * (taps at offsets -1, 0); block_n in {32, 64, 96, 128} output channels per workgroup divides n_pad. */
+  int B, H, W, kh, kw, block_n;
+  /* Epilogue, activation and scale: value = act(acc * d_wscale[n] + d_bias[n]) * out_scale, activation 0 none, 1 relu,
+   * 2 sigmoid, 3 tanh, which epilogue 0 stores to any of the S32, fp32 and encoder destinations below; epilogues 1 and 2
+   * are the GRU's, OFLOW_EPI_FLOW_HEAD the flow head's (both below; the GRU epilogues ignore activation). */
+  int epilogue, activation;
+  float out_scale;
+  /* S32 and fp32 destinations (epilogue 0; at least one destination of this or the encoder group): S32 d_y0 (and d_y1)
+   * for channels n < N (16-B aligned, pixel strides % 128 == 0), and / or fp32 NCHW d_f32 (batch / channel strides in
+   * floats; f32_accumulate = 1 adds to it). */
+  void *d_y0, *d_y1;
+  long long y0_pixel_stride, y1_pixel_stride;
+  float* d_f32;
+  long long f32_batch_stride, f32_channel_stride;
+  int f32_accumulate;
+  /* GRU (block_n 128, 1x5 / 5x1; d_gru_h, d_gru_z [P][CH] fp32, CH = gru_channels, CH % 8 == 0, read / written as
+   * 16-B vectors: both 16-byte aligned, else OFLOW_E_ALIGN):
+   *   epilogue 1 (gates, N = 2*CH): n < CH -> z = sigmoid(.) into d_gru_z;
+   *     n >= CH -> sigmoid(.) * d_gru_h[p][n-CH] into S32 d_y0 channel n-CH                      (update.py:91-96)
+   *   epilogue 2 (candidate, N = CH): h = (1 - z) * h + z * tanh(.), in place in d_gru_h and into S32 d_y0
+   *     (update.py:96-97). */
+  float *d_gru_h, *d_gru_z;
+  int gru_channels;
+  /* Encoder options (epilogue 0 only):
+   *   d_nhwc : fp32 [P][nhwc_pixel_stride] copy of the value (after activation / residual); 16-B aligned,
+   *            nhwc_pixel_stride >= N, a multiple of 4;
+   *   d_stats: per-tile instance-norm partials (count, mean, M2) of the pre-activation conv output, layout
+   *            [B][ceil(H/4)*ceil(W/32)][n_pad][3] floats (reduced by oflow_norm_stats_finalize);
+   *   d_res  : S32 residual added after the activation, then res_activation (relu(x + y), extractor.py:90);
+   *   s2d    : S32 destinations in space-to-depth layout (pixel (y/2, x/2), channel + ((y%2)*2 + x%2) * N), the input
+   *            form of the next stage's stride-2 convolutions (a 3x3/2 conv = a 2x2/1 conv on s2d input, a 1x1/2 conv =
+   *            a 1x1 conv over the first N channels of it); H, W even, N % 8 == 0. */
+  float *d_nhwc, *d_stats;
+  const void* d_res;
+  long long res_pixel_stride;
+  int nhwc_pixel_stride, res_activation, s2d;
+  /* Addend (GRU epilogues only): fp32 NHWC d_addend[P * addend_pixel_stride + n] added to the pre-activation value
+   * after the scale and bias (16-B aligned, addend_pixel_stride >= N, a multiple of 4, N % 8 == 0). It carries the
+   * GRU's loop-invariant context term: x = [inp | motion] (update.py:153-154) and inp never changes across iterations
+   * (raft.py:115-118), so W_inp * inp + bias is computed once per forward and the per-iteration z / r / q convolutions
+   * (update.py:92-105) run over [h | motion | flow] only. */
+  const float* d_addend;
+  long long addend_pixel_stride;
+  /* Split-K over the input groups for the register-direct kernels (S32 input, d_wfrag given, in_groups even; a 4-pair
+   * lane's GRU q / motion convs fill 224 of 512 two-per-CU slots unsplit). Each 4 x 32-pixel tile (x block_n channels)
+   * runs as two workgroups, each summing half of the input groups; the first to finish hands its fp32 partials to the
+   * second through d_ksplit_slab (write-through stores, an agent-scope counter, an acquire on the reader), which adds
+   * them and runs the epilogue. The split regroups the whole reduction over the input groups -- each output is the sum
+   * of two half-sums, not one running sum -- so it is not bit-identical to the unsplit call: both lie within the conv's
+   * float64 bound, 2e-6 * conv(|x|, |w|) + 1e-6, of the exact result and of each other (asserted by
+   * tests/test_gpu_conv_ksplit.py). The result does not depend on which workgroup finishes first.
+   *   d_ksplit_slab: >= ksplit_tiles * 128 * block_n floats, 16-B aligned, any contents;
+   *   d_ksplit_ctr : 2 * ksplit_tiles uint32, 8-B aligned, ZEROED ONCE before the first call; the counters only grow
+   *     (two tickets and one publication per tile and call), so successive calls and graph replays need no reset -- but
+   *     calls that share a buffer pair must be stream-ordered (never in flight together);
+   *   ksplit_tiles : capacity; OFLOW_E_SHAPE if the call needs B * ceil(H/4) * ceil(W/32) * n_pad / block_n more.
+   * A split call always runs the default 4-row tiles, small grids included (so that a caller deciding the split from
+   * its whole batch gets the same bits from any partition of it into calls); calls of other shapes (not
+   * register-direct, odd in_groups) run unsplit. Both pointers NULL: no split. */
+  float* d_ksplit_slab;
+  unsigned int* d_ksplit_ctr;
+  long long ksplit_tiles;
+  /* Flow head (epilogue OFLOW_EPI_FLOW_HEAD): update.py:31-37, conv2(relu(conv1(x))), with its 256 -> 2 output conv
+   * folded into conv1's epilogue. The call is conv1 (3x3, S32 input, N = n_pad = 256, activation 1 = ReLU, out_scale 1,
+   * block_n 64 or 128; 128 needs d_wfrag); relu(conv1) is never stored. Per pixel and 64-channel slab the epilogue
+   * forms the 18 per-tap products of conv2 at that INPUT pixel,
+   *   d_fh_partial[slab][b][t*2 + c][y][x] = sum_{ch in slab} relu(conv1)[b][slab*64 + ch][y][x] * W2[c][slab*64 + ch][ky][kx],
+   *   t = ky*3 + kx   (fp32, [fh_slabs][B][18][H][W], every in-image element written on every call),
+   * as fp32 FMAs on the fp32 values (nothing is re-split to fp16) in an order that depends on the channel's index
+   * within the slab only -- two fmaf chains over the slab's even and odd channels, each ascending, then even + odd --
+   * so every block_n and weight staging gives the same bits. oflow_flow_head_finish_f32 gathers the taps and slabs.
+   *   d_fh_weights: conv2's weight (2, 256, 3, 3) repacked [slab 4][channel 64][t*2 + c] fp32;
+   *   fh_slabs    : N / 64 = 4 (else OFLOW_E_SHAPE).
+   * Every destination of the other epilogues, d_addend and the split-K buffers must be NULL (OFLOW_E_MODE). Always the
+   * default 4 x 32 tiles, small grids included. Any other epilogue ignores these three fields. */
+  const float* d_fh_weights;
+  float* d_fh_partial;
+  int fh_slabs;
+} oflow_conv_s32_desc;
+int oflow_conv_s32(const oflow_conv_s32_desc* desc, void* stream);
+
 /* oflow_flow_head2_s32: the flow head's output conv (update.py:35-36 conv2: 3x3, C -> 2, zero padding) added into
  * coords (B, 2, H, W) fp32 in place (raft.py:133 `coords1 = coords1 + delta_flow`), from an S32 input of in_groups
  * groups (1..8): fp32 FMAs on the exact S32 values; d_weight (2, C, 3, 3) fp32 as the nn.Conv2d stores it, d_bias [2].
@@ -230,7 +339,7 @@ int oflow_flow_prep_s32(const float* d_coords, int B, int H, int W, void* d_patc
  * delta_flow) as a 1x1 conv C -> 18 per-tap products (oflow_conv_s32 with an fp32 NCHW destination d_y (B, 18, H, W))
  * followed by this gather. */
 int oflow_flow_head_col2im_f32(const float* d_y, const float* d_bias, int B, int H, int W, float* d_coords, void* stream);
-/* oflow_flow_head_finish_f32: the second half of the flow head folded into conv1 (oflow_conv_s32_ex6,
+/* oflow_flow_head_finish_f32: the second half of the flow head folded into conv1 (oflow_conv_s32,
  * OFLOW_EPI_FLOW_HEAD) and the next iteration's flow channels. Per pixel and output channel c, in this order:
  *   s = 0; for t = 0..8 (ky = t / 3, kx = t % 3), for slab = 0..slabs-1:
  *     s += d_partial[slab][b][t*2 + c][y + ky - 1][x + kx - 1]   (neighbours outside the image contribute nothing);
@@ -286,7 +395,7 @@ int oflow_flow_head2_tiled_s32(const void* d_x, long long x_pixel_stride, int in
 /* oflow_corr_lookup_tiled_nhwc_f32: the tiled lookup as fp32 NHWC rows [B*H*W][row_floats] (d_out 16-B aligned) in the
  * reference's channel order: row q, channel l*(2r+1)^2 + k = oflow_corr_lookup_tiled_f32's (b, l*(2r+1)^2 + k, y, x) bit for
  * bit; row_floats >= num_levels*(2r+1)^2, channels past that are not written. With row_floats = num_levels*(2r+1)^2 (324)
- * it is the RAFT forward's convc1 input (oflow_conv_s32_ex2, OFLOW_IN_F32). Replaces corr.py:56-77 + the permute feeding
+ * it is the RAFT forward's convc1 input (oflow_conv_s32, OFLOW_IN_F32). Replaces corr.py:56-77 + the permute feeding
  * update.py:120-121. */
 int oflow_corr_lookup_tiled_nhwc_f32(const float* const* d_levels, const int* level_h, const int* level_w, int num_levels,
                                      const float* d_coords, int B, int H, int W, int radius, float* d_out, int row_floats,
@@ -308,33 +417,6 @@ int oflow_corr_lookup_convc1_s32(const float* const* d_levels, const int* level_
 /*
  * Encoders on the split-fp16 path (methods/raft/model/extractor.py:35-231; csrc/encoder_s32.hip).
  *
- * oflow_conv_s32_ex: oflow_conv_s32 plus (epilogue 0 only)
- *   d_nhwc        : fp32 [P][nhwc_pixel_stride] copy of the value (after activation / residual);
- *   d_stats       : per-tile instance-norm partials (count, mean, M2) of the pre-activation conv output, layout
- *                   [B][ceil(H/4)*ceil(W/32)][n_pad][3] floats (reduced by oflow_norm_stats_finalize);
- *   d_res         : S32 residual added after the activation, then res_activation (relu(x + y), extractor.py:90);
- *   s2d           : S32 destinations in space-to-depth layout (pixel (y/2, x/2), channel + ((y%2)*2 + x%2) * N), the
- *                   input form of the next stage's stride-2 convolutions (a 3x3/2 conv = a 2x2/1 conv on s2d input,
- *                   a 1x1/2 conv = a 1x1 conv over the first N channels of it).  kh x kw also allows 2x2 (taps at
- *                   offsets -1, 0), block_n also 96.
- * oflow_conv_s32_ex2: oflow_conv_s32_ex with an input format: OFLOW_IN_S32 (as _ex); OFLOW_IN_F32_NORM: the raw fp32
- *   NHWC output [P][in_groups*32] of the previous convolution (x_pixel_stride = in_groups*128), normalised and ReLU'd
- *   while staged, x = max(0, raw * d_in_scale[b, c] + d_in_shift[b, c]) ([B][in_groups*32] each) -- the instance
- *   norm + ReLU between a residual block's two 3x3 convs (extractor.py:75-76) never materialises (3x3, epilogue 0,
- *   in_groups <= 4); OFLOW_IN_F32: an fp32 NHWC input of cin = x_pixel_stride/4 channels per pixel
- *   ((in_groups-1)*32 < cin <= in_groups*32, x_pixel_stride % 16 == 0; channels past cin stage as zeros) split into
- *   hi + lo while staged (1x1, epilogue 0, block_n 128: convc1 reading oflow_corr_lookup_tiled_nhwc_f32's rows).
- *   OFLOW_IN_IMG7S2: the encoders' stem (extractor.py:186, a 7x7 / stride 2 / pad 3 conv of a 3-channel image) straight
- *   from the fp32 NCHW image d_x (B, 3, 2H, 2W) for an output of H x W (x_pixel_stride ignored): each 4 x 32 output tile
- *   stages its 13 x 69 x 3 input window in LDS and builds the patch-matrix operand (channel t*3 + c, t = ky*7 + kx,
- *   in_groups 5 = 160 channels, weights packed with patches=True as for oflow_stem_patches_s32's matrix) from it, so
- *   no patch matrix is written (1x1 geometry, epilogue 0, block_n 64).
- *   OFLOW_IN_FLOW7: the motion encoder's convf1 (update.py:116, a 7x7 / stride 1 / pad 3 conv of the 2-channel flow)
- *   straight from coords1 d_x (B, 2, H, W) fp32 (x_pixel_stride ignored): flow = coords1 - the pixel grid (raft.py:129,
- *   the fp32 subtraction of oflow_flow_prep_s32), each 4 x 32 output tile stages its 10 x 38 x 2 flow window in LDS
- *   and builds the patch operand (channel t*2 + c, t = ky*7 + kx, in_groups 4 = 128 channels, weights packed with
- *   patches=True as for oflow_flow_prep_s32's matrix) from it: bit for bit the conv of that matrix, which is then not
- *   written (1x1 geometry, epilogue 0, block_n 128).
  * oflow_stem_patches_s32: 7x7/2 pad-3 patch matrix of a (B, C, H, W) fp32 image: S32 (B, ceil(H/2), ceil(W/2),
  *   out_groups) with channel t*C + c (t = ky*7 + kx), zeros past 49*C.
  * oflow_norm_stats_finalize: merge the partials (fp64 sums) -> alpha = 1/sqrt(var + eps), beta = -mean * alpha, [B][C].
@@ -342,99 +424,6 @@ int oflow_corr_lookup_convc1_s32(const float* const* d_levels, const int* level_
  *   res_mode 2: y = res_act((x2*alpha2 + beta2) + y); res_mode 3: y = res_act(relu(x2*alpha2 + beta2) + y) (a block
  *   input kept as raw fp32 + its norm); written as S32 (s2d: space-to-depth as above).
  */
-int oflow_conv_s32_ex(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack, int n_pad,
-                      const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh, int kw,
-                      int block_n, int epilogue, int activation, float out_scale, void* d_y0, long long y0_pixel_stride,
-                      void* d_y1, long long y1_pixel_stride, float* d_f32, long long f32_batch_stride,
-                      long long f32_channel_stride, int f32_accumulate, float* d_gru_h, float* d_gru_z,
-                      int gru_channels, float* d_nhwc, int nhwc_pixel_stride, float* d_stats, const void* d_res,
-                      long long res_pixel_stride, int res_activation, int s2d, void* stream);
-int oflow_conv_s32_ex2(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack, int n_pad,
-                       const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh, int kw,
-                       int block_n, int epilogue, int activation, float out_scale, void* d_y0, long long y0_pixel_stride,
-                       void* d_y1, long long y1_pixel_stride, float* d_f32, long long f32_batch_stride,
-                       long long f32_channel_stride, int f32_accumulate, float* d_gru_h, float* d_gru_z,
-                       int gru_channels, float* d_nhwc, int nhwc_pixel_stride, float* d_stats, const void* d_res,
-                       long long res_pixel_stride, int res_activation, int s2d, int in_format,
-                       const float* d_in_scale, const float* d_in_shift, void* stream);
-/* oflow_conv_s32_ex3: oflow_conv_s32_ex2 plus an fp32 NHWC addend d_addend[P * addend_pixel_stride + n] added to the
- * pre-activation value after the scale and bias (GRU epilogues 1 and 2 only; 16-B aligned, addend_pixel_stride >= N,
- * a multiple of 4; NULL = none). It carries the GRU's loop-invariant context term: x = [inp | motion] (update.py:153-154)
- * and inp never changes across iterations (raft.py:115-118), so W_inp * inp + bias is computed once per forward and the
- * per-iteration z / r / q convolutions (update.py:92-105) run over [h | motion | flow] only. */
-int oflow_conv_s32_ex3(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack, int n_pad,
-                       const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh, int kw,
-                       int block_n, int epilogue, int activation, float out_scale, void* d_y0, long long y0_pixel_stride,
-                       void* d_y1, long long y1_pixel_stride, float* d_f32, long long f32_batch_stride,
-                       long long f32_channel_stride, int f32_accumulate, float* d_gru_h, float* d_gru_z,
-                       int gru_channels, float* d_nhwc, int nhwc_pixel_stride, float* d_stats, const void* d_res,
-                       long long res_pixel_stride, int res_activation, int s2d, int in_format,
-                       const float* d_in_scale, const float* d_in_shift, const float* d_addend,
-                       long long addend_pixel_stride, void* stream);
-/* oflow_conv_s32_ex4: oflow_conv_s32_ex3 plus d_wfrag, an optional fragment-major copy of d_wpack (same bytes, reordered
- * [group][tap][n/32][slice][hi|lo][k half][row][8] so that one wave's 32x16 MFMA B fragment is 1 KB contiguous and is
- * loaded straight into registers, skipping the LDS staging of B). Used, on S32 input without instance-norm partials
- * outside the small-grid tiles, by every multi-tap convolution with block_n 128 and by 3x3 convolutions with block_n 64
- * or 32; other shapes ignore it. The block_n 64 / 32 register-direct variants measured slower in the RAFT step
- * (DESIGN.md §4, r04): pass NULL for them unless comparing (the Python layer passes d_wfrag for them only under
- * OFLOW_CONV_BREG64 / OFLOW_CONV_BREG32). NULL = ex3. */
-int oflow_conv_s32_ex4(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack, int n_pad,
-                       const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh, int kw,
-                       int block_n, int epilogue, int activation, float out_scale, void* d_y0, long long y0_pixel_stride,
-                       void* d_y1, long long y1_pixel_stride, float* d_f32, long long f32_batch_stride,
-                       long long f32_channel_stride, int f32_accumulate, float* d_gru_h, float* d_gru_z,
-                       int gru_channels, float* d_nhwc, int nhwc_pixel_stride, float* d_stats, const void* d_res,
-                       long long res_pixel_stride, int res_activation, int s2d, int in_format,
-                       const float* d_in_scale, const float* d_in_shift, const float* d_addend,
-                       long long addend_pixel_stride, const void* d_wfrag, void* stream);
-/* oflow_conv_s32_ex5: oflow_conv_s32_ex4 plus split-K over the input groups for the register-direct kernels (S32 input,
- * d_wfrag given, in_groups even; the 224-workgroup GRU q / motion convs of a 4-pair lane fill 224 of 512 two-per-CU
- * slots unsplit). Each 4 x 32-pixel tile (x block_n channels) runs as two workgroups, each summing half of the input
- * groups; the first to finish hands its fp32 partials to the second through d_ksplit_slab (write-through stores, an
- * agent-scope counter, an acquire on the reader), which adds them and runs the epilogue. Results differ from ex4 only
- * in the order of one fp32 addition per output (and do not depend on which workgroup finishes first).
- *   d_ksplit_slab: >= ksplit_tiles * 128 * block_n floats, 16-B aligned, any contents;
- *   d_ksplit_ctr: 2 * ksplit_tiles uint32, 8-B aligned, ZEROED ONCE before the first call; the counters only grow (two
- *     tickets and one publication per tile and call), so successive calls and graph replays need no reset -- but
- *     calls that share a buffer pair must be stream-ordered (never in flight together);
- *   ksplit_tiles: capacity; OFLOW_E_SHAPE if the call needs B * ceil(H/4) * ceil(W/32) * n_pad / block_n more.
- * A split call always runs the default 4-row tiles, small grids included (so that a caller deciding the split from its
- * whole batch gets the same bits from any partition of it into calls); calls of other shapes (not register-direct, odd
- * in_groups) run unsplit. Both NULL = ex4. */
-int oflow_conv_s32_ex5(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack, int n_pad,
-                       const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh, int kw,
-                       int block_n, int epilogue, int activation, float out_scale, void* d_y0, long long y0_pixel_stride,
-                       void* d_y1, long long y1_pixel_stride, float* d_f32, long long f32_batch_stride,
-                       long long f32_channel_stride, int f32_accumulate, float* d_gru_h, float* d_gru_z,
-                       int gru_channels, float* d_nhwc, int nhwc_pixel_stride, float* d_stats, const void* d_res,
-                       long long res_pixel_stride, int res_activation, int s2d, int in_format,
-                       const float* d_in_scale, const float* d_in_shift, const float* d_addend,
-                       long long addend_pixel_stride, const void* d_wfrag, float* d_ksplit_slab,
-                       unsigned* d_ksplit_ctr, long long ksplit_tiles, void* stream);
-/* oflow_conv_s32_ex6: oflow_conv_s32_ex5 plus epilogue OFLOW_EPI_FLOW_HEAD: the flow head (update.py:31-37,
- * conv2(relu(conv1(x)))) with its 256 -> 2 output conv folded into conv1's epilogue. The call is conv1 (3x3, S32 input,
- * N = n_pad = 256, activation 1 = ReLU, out_scale 1, block_n 64 or 128; 128 needs d_wfrag); relu(conv1) is never
- * stored. Per pixel and 64-channel slab the epilogue forms the 18 per-tap products of conv2 at that INPUT pixel,
- *   d_fh_partial[slab][b][t*2 + c][y][x] = sum_{ch in slab} relu(conv1)[b][slab*64 + ch][y][x] * W2[c][slab*64 + ch][ky][kx],
- *   t = ky*3 + kx   (fp32, [fh_slabs][B][18][H][W], every in-image element written on every call),
- * as fp32 FMAs on the fp32 values (nothing is re-split to fp16) in an order that depends on the channel's index within
- * the slab only -- two fmaf chains over the slab's even and odd channels, each ascending, then even + odd -- so every
- * block_n and weight staging gives the same bits. oflow_flow_head_finish_f32 gathers the taps and slabs.
- *   d_fh_weights: conv2's weight (2, 256, 3, 3) repacked [slab 4][channel 64][t*2 + c] fp32;
- *   fh_slabs: N / 64 = 4 (else OFLOW_E_SHAPE). Every destination of the other epilogues, d_addend and the split-K
- *   buffers must be NULL (OFLOW_E_MODE). Always the default 4 x 32 tiles, small grids included.
- * Any other epilogue: oflow_conv_s32_ex5 (the three flow-head arguments ignored). */
-int oflow_conv_s32_ex6(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack, int n_pad,
-                       const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh, int kw,
-                       int block_n, int epilogue, int activation, float out_scale, void* d_y0, long long y0_pixel_stride,
-                       void* d_y1, long long y1_pixel_stride, float* d_f32, long long f32_batch_stride,
-                       long long f32_channel_stride, int f32_accumulate, float* d_gru_h, float* d_gru_z,
-                       int gru_channels, float* d_nhwc, int nhwc_pixel_stride, float* d_stats, const void* d_res,
-                       long long res_pixel_stride, int res_activation, int s2d, int in_format,
-                       const float* d_in_scale, const float* d_in_shift, const float* d_addend,
-                       long long addend_pixel_stride, const void* d_wfrag, float* d_ksplit_slab,
-                       unsigned* d_ksplit_ctr, long long ksplit_tiles, const float* d_fh_weights, float* d_fh_partial,
-                       int fh_slabs, void* stream);
 int oflow_stem_patches_s32(const float* d_img, int B, int C, int H, int W, void* d_out, int out_groups, void* stream);
 int oflow_norm_stats_finalize(const float* d_partials, int B, int tiles, int n_pad, int C, double eps, float* d_alpha,
                               float* d_beta, void* stream);

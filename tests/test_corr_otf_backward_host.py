@@ -96,7 +96,7 @@ def test_symbol_and_ops_are_declared_and_listed():
     assert "oflow_corr_lookup_otf_backward_f32" in _native.SYMBOLS
     assert "corr_lookup_alt" in _ops.OPS and "corr_lookup_alt_backward" in _ops.OPS
     lib = _native.load()
-    assert lib.oflow_corr_lookup_otf_backward_f32 is not None and lib.oflow_abi_version() == 1
+    assert lib.oflow_corr_lookup_otf_backward_f32 is not None and lib.oflow_abi_version() == _native.ABI_VERSION
     for name in ("corr_lookup_alt", "corr_lookup_alt_backward"):
         assert getattr(torch.ops.oflow, name).default._schema.name == f"oflow::{name}"
 

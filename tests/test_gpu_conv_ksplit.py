@@ -1,10 +1,11 @@
-"""Split-K register-direct convolutions (oflow_conv_s32_ex5, include/oflow.h; csrc/conv_s32.hip): each 4 x 32-pixel
+"""Split-K register-direct convolutions (oflow_conv_s32 split-K, include/oflow.h; csrc/conv_s32.hip): each 4 x 32-pixel
 tile runs as two workgroups over half the input groups each, meeting through an fp32 slab and agent-scope counters.
 The RAFT update uses it for the motion conv and both GRU candidate convs (update.py:91-128; model/update.py
 KSPLIT_LAYERS). Checked against a float64 conv of the same split operands (the conv_s32 bound), against the unsplit
 kernel, exactly on small integers, across repeated calls sharing one scratch (counters that only grow), on two
 streams at once. The RAFT forward leaves it off by default (model/update.py KSPLIT_LAYERS: slower in the two-lane step);
 test_raft_with_ksplit_matches_reference_flows runs the benchmarked forward with it on against the reference's flows."""
+import ctypes
 import math
 
 import pytest
@@ -169,14 +170,21 @@ def test_ksplit_arg_errors():
     f = torch.empty(b, 128, h, w, device=DEV)
     ks = N.KSplit(b, h, w, DEV)
     xv = N.S32Slice(x)
-    args = [xv.ptr, xv.ps, 8, cw.pack.data_ptr(), 128, cw.wscale.data_ptr(), None, 128, b, h, w, 3, 3, 128,
-            0, 0, 1.0, None, 0, None, 0, f.data_ptr(), f.stride(0), f.stride(1), 0, None, None, 0, None, 0, None, None, 0,
-            0, 0, 0, None, None, None, 0, cw.frag().data_ptr()]
+    desc = N.ConvS32Desc(
+        struct_size=ctypes.sizeof(N.ConvS32Desc), d_x=xv.ptr, x_pixel_stride=xv.ps, in_groups=8, d_wpack=cw.pack.data_ptr(),
+        d_wfrag=cw.frag().data_ptr(), n_pad=128, d_wscale=cw.wscale.data_ptr(), N=128, B=b, H=h, W=w, kh=3, kw=3,
+        block_n=128, out_scale=1.0, d_f32=f.data_ptr(), f32_batch_stride=f.stride(0), f32_channel_stride=f.stride(1),
+    )
     stream = torch.cuda.current_stream(DEV).cuda_stream
-    assert lib.oflow_conv_s32_ex5(*args, ks.slab.data_ptr(), None, ks.tiles, stream) == -1  # OFLOW_E_NULL
-    assert lib.oflow_conv_s32_ex5(*args, ks.slab.data_ptr() + 4, ks.ctr.data_ptr(), ks.tiles, stream) == -7  # OFLOW_E_ALIGN
-    assert lib.oflow_conv_s32_ex5(*args, ks.slab.data_ptr(), ks.ctr.data_ptr(), 0, stream) == -2  # OFLOW_E_SHAPE
-    assert lib.oflow_conv_s32_ex5(*args, ks.slab.data_ptr(), ks.ctr.data_ptr(), ks.tiles, stream) == 0
+
+    def status(slab, ctr, tiles):
+        desc.d_ksplit_slab, desc.d_ksplit_ctr, desc.ksplit_tiles = slab, ctr, tiles
+        return lib.oflow_conv_s32(ctypes.byref(desc), stream)
+
+    assert status(ks.slab.data_ptr(), None, ks.tiles) == -1  # OFLOW_E_NULL
+    assert status(ks.slab.data_ptr() + 4, ks.ctr.data_ptr(), ks.tiles) == -7  # OFLOW_E_ALIGN
+    assert status(ks.slab.data_ptr(), ks.ctr.data_ptr(), 0) == -2  # OFLOW_E_SHAPE
+    assert status(ks.slab.data_ptr(), ks.ctr.data_ptr(), ks.tiles) == 0
     torch.cuda.synchronize()
 
 

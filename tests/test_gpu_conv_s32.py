@@ -172,7 +172,7 @@ def _gru_epilogues():
 def test_conv_s32_gru_hoisted_context(kh, kw):
     """The GRU with its loop-invariant context term hoisted (update.py:92-105, x = [inp | motion], inp constant):
     W_inp * inp + bias once (epilogue 0, fp32 NHWC [P, 384] = z | r | q), then the z|r and q convs over
-    [h | motion | flow] only with that addend in their epilogues (oflow_conv_s32_ex3) -- against the full 384-channel
+    [h | motion | flow] only with that addend in their epilogues (d_addend) -- against the full 384-channel
     SepConvGRU step in float64."""
     g = torch.Generator().manual_seed(17 + kh)
     b, h, w, ch = 2, 9, 37, 128
@@ -319,7 +319,7 @@ def test_flow_prep_tiled_equals_per_thread(b, h, w):
 
 @pytest.mark.parametrize("c,n,bn", [(64, 64, 64), (96, 96, 96), (128, 128, 128)])
 def test_conv_normalise_on_load_equals_norm_apply(c, n, bn):
-    """oflow_conv_s32_ex2 with a raw fp32 NHWC input normalised + ReLU'd while staged (NhwcNormIn) equals the
+    """OFLOW_IN_F32_NORM: a conv with a raw fp32 NHWC input normalised + ReLU'd while staged (NhwcNormIn) equals the
     two-pass path: norm_apply -> S32 -> conv (extractor.py:75-76 between a block's two convs)."""
     b, h, w = 2, 37, 70
     g = torch.Generator().manual_seed(5)
@@ -543,7 +543,7 @@ def test_flow_head_col2im_matches_fp64_and_conv(b, h, w):
     (3, 3, 256, 2, 32, 0, False, 2, 55, 128),      # the flow head's output conv (CONV_BREG32: 4 x 1 waves)
 ])
 def test_conv_register_weights_bit_identical(monkeypatch, kh, kw, cin, n, bn, epi, stats, b, h, w):
-    """The register-direct weight path (ConvWeights.frag -> oflow_conv_s32_ex4, BREG kernels; grids over 16384 output
+    """The register-direct weight path (ConvWeights.frag -> d_wfrag, BREG kernels; grids over 16384 output
     pixels at block_n 128, no instance-norm partials) against the LDS-staged one: the same MFMAs in the same order per
     output, so every output bit-identical; plus the fp64 bound of test_conv_s32_matches_fp64 for the plain epilogue."""
     g = torch.Generator().manual_seed(kh * 100 + cin + epi + n)

@@ -1,4 +1,4 @@
-"""The flow head with its 256 -> 2 output conv folded into conv1's epilogue (oflow_conv_s32_ex6 with
+"""The flow head with its 256 -> 2 output conv folded into conv1's epilogue (oflow_conv_s32 with
 OFLOW_EPI_FLOW_HEAD, csrc/conv_s32.hip; oflow_flow_head_finish_f32, csrc/s32_io.hip; FLOW_HEAD_MODE "fused").
 
 Reference: ``coords + F.conv2d(relu(conv1(x)), w2, b2, padding=1)`` in float64 on the exact fp32 relu(conv1) values

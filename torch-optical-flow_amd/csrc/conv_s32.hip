@@ -120,18 +120,18 @@ struct ConvArgs {
   int wbytes;              // bytes of the packed weights (kg * taps * npad * 128)
   const uint8_t* wf;       // the same weights fragment-major (register-direct B, BREG kernels), or null
   int exp_flags;           // experiments only (oflow_exp_set_conv_flags): bit 0 = the stem's element-wise window loop
-  // split-K (BREG kernels only, oflow_conv_s32_ex5): gridDim.z = 2 workgroups per tile, each summing half of the input
+  // split-K (BREG kernels only, d_ksplit_slab / d_ksplit_ctr): gridDim.z = 2 workgroups per tile, each summing half of the input
   // groups (kg above is the half); per tile a BM x BN fp32 partial slab and two counters [ticket, published]
   float* ks_slab;
   unsigned* ks_ctr;
   long long ks_tiles;      // tiles (x channel blocks) the slab and counters hold
-  // flow-head epilogue (EPI 3, oflow_conv_s32_ex6): the output conv's weights [slab][64][18] and the per-tap partial
+  // flow-head epilogue (EPI 3, OFLOW_EPI_FLOW_HEAD): the output conv's weights [slab][64][18] and the per-tap partial
   // sums [slabs][B][18][H][W] (fp32)
   const float* fhw;
   float* fhy;
 };
 constexpr int kEpiFlowHead = OFLOW_EPI_FLOW_HEAD;
-// input formats of oflow_conv_s32_ex2
+// input formats (oflow_conv_s32_desc.in_format)
 constexpr int kInS32 = OFLOW_IN_S32, kInF32Norm = OFLOW_IN_F32_NORM, kInF32 = OFLOW_IN_F32, kInImg = OFLOW_IN_IMG7S2,
               kInFlow = OFLOW_IN_FLOW7;
 // kInImg: the stem's 7x7/2 pad-3 window of a 3-channel image, staged per tile (TY = 4 rows x 32 columns)
@@ -1438,73 +1438,156 @@ int dispatch_conv(const ConvArgs& a, int kh, int kw, int block_n, int epilogue, 
   }
 }
 
-// argument checks + ConvArgs for oflow_conv_s32_ex
-int build_conv_args(ConvArgs& a, const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack,
-                    int n_pad, const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh, int kw,
-                    int block_n, int epilogue, int activation, float out_scale, void* d_y0, long long y0_pixel_stride,
-                    void* d_y1, long long y1_pixel_stride, float* d_f32, long long f32_batch_stride,
-                    long long f32_channel_stride, int f32_accumulate, float* d_gru_h, float* d_gru_z, int gru_channels,
-                    float* d_nhwc, int nhwc_pixel_stride, float* d_stats, const void* d_res, long long res_pixel_stride,
-                    int res_activation, int s2d) {
-  if (!d_x || !d_wpack || !d_wscale) return OFLOW_E_NULL;
-  if (B <= 0 || H <= 0 || W <= 0 || N <= 0 || in_groups <= 0 || n_pad < N || n_pad % block_n) return OFLOW_E_SHAPE;
-  if (activation < 0 || activation > 3 || res_activation < 0 || res_activation > 3 || epilogue < 0 || epilogue > 2)
+// every argument check of oflow_conv_s32, in the order that decides which status a call with several errors gets, and
+// the ConvArgs of a valid call
+int conv_args_from_desc(const oflow_conv_s32_desc& d, ConvArgs& a) {
+  const bool fh = d.epilogue == kEpiFlowHead;
+  if (fh) {
+    // the flow-head epilogue: 3x3 conv 32 * in_groups -> 256 on S32 input, ReLU; its only outputs are the partial sums
+    if (!d.d_fh_weights || !d.d_fh_partial) return OFLOW_E_NULL;
+    if (d.N != 256 || d.n_pad != 256 || d.fh_slabs != d.N / 64 || d.kh != 3 || d.kw != 3 ||
+        (d.block_n != 64 && d.block_n != 128))
+      return OFLOW_E_SHAPE;
+    if (d.in_format != kInS32 || d.activation != 1 || d.out_scale != 1.0f || d.d_y0 || d.d_y1 || d.d_f32 || d.d_gru_h ||
+        d.d_gru_z || d.d_nhwc || d.d_stats || d.d_res || d.s2d || d.d_addend || d.d_ksplit_slab || d.d_ksplit_ctr)
+      return OFLOW_E_MODE;
+    if ((d.x_pixel_stride & 127) || ((uintptr_t)d.d_fh_weights & 3) || ((uintptr_t)d.d_fh_partial & 3)) return OFLOW_E_ALIGN;
+  }
+  const bool gru = d.epilogue == 1 || d.epilogue == 2;
+  if (!d.d_x || !d.d_wpack || !d.d_wscale) return OFLOW_E_NULL;
+  if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.N <= 0 || d.in_groups <= 0 || d.n_pad < d.N || d.n_pad % d.block_n)
+    return OFLOW_E_SHAPE;
+  // (the flow head takes no residual: its res_activation is not looked at)
+  if (d.activation < 0 || d.activation > 3 ||
+      (!fh && (d.res_activation < 0 || d.res_activation > 3 || d.epilogue < 0 || d.epilogue > 2)))
     return OFLOW_E_MODE;
-  if ((x_pixel_stride & 15) || ((uintptr_t)d_x & 15) || ((uintptr_t)d_wpack & 15)) return OFLOW_E_ALIGN;
-  if (epilogue == 0 && !d_y0 && !d_f32 && !d_nhwc && !d_stats) return OFLOW_E_NULL;
-  if (epilogue != 0 && (!d_y0 || !d_gru_h || !d_gru_z || gru_channels <= 0 || gru_channels % 8)) return OFLOW_E_NULL;
+  if ((d.x_pixel_stride & 15) || ((uintptr_t)d.d_x & 15) || ((uintptr_t)d.d_wpack & 15)) return OFLOW_E_ALIGN;
+  if (d.epilogue == 0 && !d.d_y0 && !d.d_f32 && !d.d_nhwc && !d.d_stats) return OFLOW_E_NULL;
+  if (gru && (!d.d_y0 || !d.d_gru_h || !d.d_gru_z || d.gru_channels <= 0 || d.gru_channels % 8)) return OFLOW_E_NULL;
   // the GRU epilogues read h / z and write z as 16-B vectors (rows of gru_channels floats, n % 8 == 0)
-  if (epilogue != 0 && (((uintptr_t)d_gru_h & 15) || ((uintptr_t)d_gru_z & 15))) return OFLOW_E_ALIGN;
-  if (epilogue == 1 && N != 2 * gru_channels) return OFLOW_E_SHAPE;
-  if (epilogue == 2 && N != gru_channels) return OFLOW_E_SHAPE;
-  if (epilogue != 0 && (d_nhwc || d_stats || d_res || s2d)) return OFLOW_E_MODE;
-  if (s2d && ((H | W) & 1 || N % 8)) return OFLOW_E_SHAPE;
-  if (d_nhwc && (nhwc_pixel_stride < N || ((uintptr_t)d_nhwc & 15) || (nhwc_pixel_stride & 3))) return OFLOW_E_ALIGN;
-  if ((d_y0 && ((y0_pixel_stride & 127) || ((uintptr_t)d_y0 & 15))) ||
-      (d_y1 && ((y1_pixel_stride & 127) || ((uintptr_t)d_y1 & 15))) ||
-      (d_res && ((res_pixel_stride & 127) || ((uintptr_t)d_res & 15))))
+  if (gru && (((uintptr_t)d.d_gru_h & 15) || ((uintptr_t)d.d_gru_z & 15))) return OFLOW_E_ALIGN;
+  if (d.epilogue == 1 && d.N != 2 * d.gru_channels) return OFLOW_E_SHAPE;
+  if (d.epilogue == 2 && d.N != d.gru_channels) return OFLOW_E_SHAPE;
+  if (gru && (d.d_nhwc || d.d_stats || d.d_res || d.s2d)) return OFLOW_E_MODE;
+  if (d.s2d && ((d.H | d.W) & 1 || d.N % 8)) return OFLOW_E_SHAPE;
+  if (d.d_nhwc && (d.nhwc_pixel_stride < d.N || ((uintptr_t)d.d_nhwc & 15) || (d.nhwc_pixel_stride & 3))) return OFLOW_E_ALIGN;
+  if ((d.d_y0 && ((d.y0_pixel_stride & 127) || ((uintptr_t)d.d_y0 & 15))) ||
+      (d.d_y1 && ((d.y1_pixel_stride & 127) || ((uintptr_t)d.d_y1 & 15))) ||
+      (d.d_res && ((d.res_pixel_stride & 127) || ((uintptr_t)d.d_res & 15))))
     return OFLOW_E_ALIGN;
   a = ConvArgs{};
-  a.x = static_cast<const uint8_t*>(d_x);
-  a.xps = x_pixel_stride;
-  a.kg = in_groups;
-  a.w = static_cast<const uint8_t*>(d_wpack);
-  a.npad = n_pad;
-  a.wsc = d_wscale;
-  a.bias = d_bias;
-  a.N = N;
-  a.B = B;
-  a.H = H;
-  a.W = W;
-  a.tiles_x = (W + kTX - 1) / kTX;
-  a.tiles_y = (H + kTY - 1) / kTY;
-  a.act = activation;
-  a.oscale = out_scale;
-  a.y0 = static_cast<uint8_t*>(d_y0);
-  a.y0ps = y0_pixel_stride;
-  a.y1 = static_cast<uint8_t*>(d_y1);
-  a.y1ps = y1_pixel_stride;
-  a.f = d_f32;
-  a.fbs = f32_batch_stride;
-  a.fcs = f32_channel_stride;
-  a.faccum = f32_accumulate;
-  a.h = d_gru_h;
-  a.z = d_gru_z;
-  a.gch = gru_channels;
-  a.fn = d_nhwc;
-  a.fnps = nhwc_pixel_stride;
-  a.stats = d_stats;
-  a.res = static_cast<const uint8_t*>(d_res);
-  a.resps = res_pixel_stride;
-  a.res_act = res_activation;
-  a.s2d = s2d;
-  a.cin = in_groups * 32;
-  // the loads address the weights and one image of the input with 32-bit offsets
-  const long long wbytes = (long long)in_groups * kh * kw * n_pad * 128;
-  if (wbytes >= (1ll << 31) || (long long)H * W * x_pixel_stride >= (1ll << 31)) return OFLOW_E_SHAPE;
-  a.wbytes = static_cast<int>(wbytes);
+  a.x = static_cast<const uint8_t*>(d.d_x);
+  a.xps = d.x_pixel_stride;
+  a.kg = d.in_groups;
+  a.w = static_cast<const uint8_t*>(d.d_wpack);
+  a.npad = d.n_pad;
+  a.wsc = d.d_wscale;
+  a.bias = d.d_bias;
+  a.N = d.N;
+  a.B = d.B;
+  a.H = d.H;
+  a.W = d.W;
+  a.tiles_x = (d.W + kTX - 1) / kTX;
+  a.tiles_y = (d.H + kTY - 1) / kTY;
+  a.act = d.activation;
+  a.oscale = d.out_scale;
+  a.cin = d.in_groups * 32;
   a.exp_flags = g_conv_exp_flags;
-  (void)block_n;
+  a.y0 = static_cast<uint8_t*>(d.d_y0);
+  a.y0ps = d.y0_pixel_stride;
+  a.y1 = static_cast<uint8_t*>(d.d_y1);
+  a.y1ps = d.y1_pixel_stride;
+  a.f = d.d_f32;
+  a.fbs = d.f32_batch_stride;
+  a.fcs = d.f32_channel_stride;
+  a.faccum = d.f32_accumulate;
+  a.h = d.d_gru_h;
+  a.z = d.d_gru_z;
+  a.gch = d.gru_channels;
+  a.fn = d.d_nhwc;
+  a.fnps = d.nhwc_pixel_stride;
+  a.stats = d.d_stats;
+  a.res = static_cast<const uint8_t*>(d.d_res);
+  a.resps = d.res_pixel_stride;
+  a.res_act = d.res_activation;
+  a.s2d = d.s2d;
+  // the loads address the weights and one image of the input with 32-bit offsets
+  const long long wbytes = (long long)d.in_groups * d.kh * d.kw * d.n_pad * 128;
+  if (wbytes >= (1ll << 31) || (long long)d.H * d.W * d.x_pixel_stride >= (1ll << 31)) return OFLOW_E_SHAPE;
+  a.wbytes = static_cast<int>(wbytes);
+  if (d.d_wfrag) {  // the fragment-major copy of d_wpack (same size; n_pad a multiple of 32)
+    if ((uintptr_t)d.d_wfrag & 15) return OFLOW_E_ALIGN;
+    if (d.n_pad % 32) return OFLOW_E_SHAPE;
+    a.wf = static_cast<const uint8_t*>(d.d_wfrag);
+  }
+  if (fh) {
+    a.fhw = d.d_fh_weights;
+    a.fhy = d.d_fh_partial;
+    return OFLOW_OK;
+  }
+  if (d.in_format < kInS32 || d.in_format > kInFlow) return OFLOW_E_MODE;
+  a.ain = d.in_format;
+  if (d.in_format == kInFlow) {  // convf1 from coords1: 1x1 geometry over 4 patch groups, BN 128, epilogue 0
+    if (d.kh != 1 || d.kw != 1 || d.epilogue != 0 || d.block_n != 128 || d.in_groups != (kImgK * kImgK * 2 + 31) / 32)
+      return OFLOW_E_MODE;
+    if ((long long)2 * d.B * d.H * d.W >= (1ll << 31) || d.d_addend) return OFLOW_E_SHAPE;
+    return OFLOW_OK;  // (no addend, no split-K)
+  }
+  if (d.in_format == kInImg) {  // the stem from the image: 1x1 geometry over 5 patch groups, BN 64, epilogue 0
+    if (d.kh != 1 || d.kw != 1 || d.epilogue != 0 || d.block_n != 64 || d.in_groups != (kImgK * kImgK * kImgC + 31) / 32)
+      return OFLOW_E_MODE;
+    if ((long long)kImgC * 4 * d.H * d.W >= (1ll << 31)) return OFLOW_E_SHAPE;
+    if (d.d_addend) return OFLOW_E_MODE;
+    return OFLOW_OK;  // (no split-K)
+  }
+  if (d.in_format != kInF32 && (d.x_pixel_stride & 127)) return OFLOW_E_ALIGN;  // S32 / dense fp32: whole 128-B groups
+  if (d.in_format == kInF32Norm && d.x_pixel_stride != (long long)d.in_groups * 128) return OFLOW_E_SHAPE;  // dense [P][kg*32]
+  if (d.in_format == kInF32) {  // rows of cin fp32 channels, (kg - 1) * 32 < cin <= kg * 32, cin % 4 == 0
+    const long long cin = d.x_pixel_stride / 4;
+    if ((d.x_pixel_stride & 15) || cin > (long long)d.in_groups * 32 || cin <= (long long)(d.in_groups - 1) * 32)
+      return OFLOW_E_SHAPE;
+    a.cin = static_cast<int>(cin);
+  }
+  if (d.in_format == kInF32Norm) {  // normalised + ReLU'd on load
+    if (!d.d_in_scale || !d.d_in_shift) return OFLOW_E_NULL;
+    if (d.kh != 3 || d.kw != 3 || d.epilogue != 0 || d.in_groups > kAinGroups) return OFLOW_E_MODE;
+    a.ia = d.d_in_scale;
+    a.ib = d.d_in_shift;
+  } else if (d.in_format == kInF32) {
+    if (d.kh != 1 || d.kw != 1 || d.epilogue != 0 || d.block_n != 128) return OFLOW_E_MODE;
+  }
+  if (d.d_addend) {  // GRU epilogues only; 16-B aligned rows of >= N floats
+    if (d.epilogue == 0) return OFLOW_E_MODE;
+    // the epilogue reads whole 8-float octets of every row: N a multiple of 8 keeps them inside the row
+    if (d.N % 8) return OFLOW_E_SHAPE;
+    if (((uintptr_t)d.d_addend & 15) || (d.addend_pixel_stride & 3) || d.addend_pixel_stride < d.N) return OFLOW_E_ALIGN;
+    a.add = d.d_addend;
+    a.addps = d.addend_pixel_stride;
+  }
+  if (d.d_ksplit_slab || d.d_ksplit_ctr) {
+    // split-K over the input groups: only the register-direct kernels (S32 input, fragment-major weights, multi-tap,
+    // 4-row tiles) take it; any other path this call would dispatch to runs unsplit (within the same float64 bound;
+    // the split regroups the sum over the input groups into two half-sums)
+    if (!d.d_ksplit_slab || !d.d_ksplit_ctr) return OFLOW_E_NULL;
+    if (((uintptr_t)d.d_ksplit_slab & 15) || ((uintptr_t)d.d_ksplit_ctr & 7)) return OFLOW_E_ALIGN;
+    if (d.ksplit_tiles <= 0) return OFLOW_E_SHAPE;
+    // (the register-direct instances: launch_bn / dispatch_conv -- 128-channel blocks of any multi-tap kernel but 2x2,
+    // 64- and 32-channel blocks of 3x3 ones; the GRU epilogues 1x5 / 5x1 only -- at the default tiles whatever the
+    // grid's size, see small_grid)
+    a.ks_slab = d.d_ksplit_slab;
+    const bool breg = d.in_format == kInS32 && a.wf != nullptr && use_breg(a, d.block_n, d.kh * d.kw) && d.kh * d.kw != 4 &&
+                      (d.block_n == 128 || (d.kh == 3 && d.kw == 3)) && (d.epilogue == 0 || d.kh * d.kw == 5);
+    a.ks_slab = nullptr;
+    if (breg && (d.in_groups % 2) == 0) {
+      // ksplit_tiles: the slab's capacity in (4 x 32-pixel tile, block_n channels) units of 128 * block_n floats
+      if ((long long)d.B * a.tiles_y * a.tiles_x * (d.n_pad / d.block_n) > d.ksplit_tiles) return OFLOW_E_SHAPE;
+      a.ks_slab = d.d_ksplit_slab;
+      a.ks_ctr = d.d_ksplit_ctr;
+      a.ks_tiles = d.ksplit_tiles;
+      a.kg = d.in_groups / 2;
+      a.wbytes /= 2;
+    }
+  }
   return OFLOW_OK;
 }
 
@@ -1514,223 +1597,13 @@ OFLOW_RANGE_FLAG_SETTER(conv)
 
 using namespace oflow;
 
-extern "C" int oflow_conv_s32_ex5(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack,
-                                  int n_pad, const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh,
-                                  int kw, int block_n, int epilogue, int activation, float out_scale, void* d_y0,
-                                  long long y0_pixel_stride, void* d_y1, long long y1_pixel_stride, float* d_f32,
-                                  long long f32_batch_stride, long long f32_channel_stride, int f32_accumulate,
-                                  float* d_gru_h, float* d_gru_z, int gru_channels, float* d_nhwc, int nhwc_pixel_stride,
-                                  float* d_stats, const void* d_res, long long res_pixel_stride, int res_activation,
-                                  int s2d, int in_format, const float* d_in_scale, const float* d_in_shift,
-                                  const float* d_addend, long long addend_pixel_stride, const void* d_wfrag,
-                                  float* d_ksplit_slab, unsigned* d_ksplit_ctr, long long ksplit_tiles, void* stream);
-
-extern "C" int oflow_conv_s32_ex4(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack,
-                                  int n_pad, const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh,
-                                  int kw, int block_n, int epilogue, int activation, float out_scale, void* d_y0,
-                                  long long y0_pixel_stride, void* d_y1, long long y1_pixel_stride, float* d_f32,
-                                  long long f32_batch_stride, long long f32_channel_stride, int f32_accumulate,
-                                  float* d_gru_h, float* d_gru_z, int gru_channels, float* d_nhwc, int nhwc_pixel_stride,
-                                  float* d_stats, const void* d_res, long long res_pixel_stride, int res_activation,
-                                  int s2d, int in_format, const float* d_in_scale, const float* d_in_shift,
-                                  const float* d_addend, long long addend_pixel_stride, const void* d_wfrag, void* stream) {
-  return oflow_conv_s32_ex5(d_x, x_pixel_stride, in_groups, d_wpack, n_pad, d_wscale, d_bias, N, B, H, W, kh, kw,
-                            block_n, epilogue, activation, out_scale, d_y0, y0_pixel_stride, d_y1, y1_pixel_stride,
-                            d_f32, f32_batch_stride, f32_channel_stride, f32_accumulate, d_gru_h, d_gru_z, gru_channels,
-                            d_nhwc, nhwc_pixel_stride, d_stats, d_res, res_pixel_stride, res_activation, s2d, in_format,
-                            d_in_scale, d_in_shift, d_addend, addend_pixel_stride, d_wfrag, nullptr, nullptr, 0, stream);
-}
-
-extern "C" int oflow_conv_s32_ex5(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack,
-                                  int n_pad, const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh,
-                                  int kw, int block_n, int epilogue, int activation, float out_scale, void* d_y0,
-                                  long long y0_pixel_stride, void* d_y1, long long y1_pixel_stride, float* d_f32,
-                                  long long f32_batch_stride, long long f32_channel_stride, int f32_accumulate,
-                                  float* d_gru_h, float* d_gru_z, int gru_channels, float* d_nhwc, int nhwc_pixel_stride,
-                                  float* d_stats, const void* d_res, long long res_pixel_stride, int res_activation,
-                                  int s2d, int in_format, const float* d_in_scale, const float* d_in_shift,
-                                  const float* d_addend, long long addend_pixel_stride, const void* d_wfrag,
-                                  float* d_ksplit_slab, unsigned* d_ksplit_ctr, long long ksplit_tiles, void* stream) {
+extern "C" int oflow_conv_s32(const oflow_conv_s32_desc* desc, void* stream) {
+  if (!desc) return OFLOW_E_NULL;
+  if (desc->struct_size != sizeof(oflow_conv_s32_desc)) return OFLOW_E_MODE;  // (before any other field is read)
   ConvArgs a;
-  const int st = build_conv_args(a, d_x, x_pixel_stride, in_groups, d_wpack, n_pad, d_wscale, d_bias, N, B, H, W, kh, kw,
-                                 block_n, epilogue, activation, out_scale, d_y0, y0_pixel_stride, d_y1, y1_pixel_stride,
-                                 d_f32, f32_batch_stride, f32_channel_stride, f32_accumulate, d_gru_h, d_gru_z,
-                                 gru_channels, d_nhwc, nhwc_pixel_stride, d_stats, d_res, res_pixel_stride,
-                                 res_activation, s2d);
+  const int st = conv_args_from_desc(*desc, a);
   if (st != OFLOW_OK) return st;
-  if (d_wfrag) {  // the fragment-major copy of d_wpack (same size; n_pad a multiple of 32)
-    if ((uintptr_t)d_wfrag & 15) return OFLOW_E_ALIGN;
-    if (n_pad % 32) return OFLOW_E_SHAPE;
-    a.wf = static_cast<const uint8_t*>(d_wfrag);
-  }
-  if (in_format < kInS32 || in_format > kInFlow) return OFLOW_E_MODE;
-  if (in_format == kInFlow) {  // convf1 from coords1: 1x1 geometry over 4 patch groups, BN 128, epilogue 0
-    if (kh != 1 || kw != 1 || epilogue != 0 || block_n != 128 || in_groups != (kImgK * kImgK * 2 + 31) / 32)
-      return OFLOW_E_MODE;
-    if ((long long)2 * B * H * W >= (1ll << 31) || d_addend) return OFLOW_E_SHAPE;
-    a.ain = in_format;
-    return dispatch_conv(a, kh, kw, block_n, epilogue, static_cast<hipStream_t>(stream));
-  }
-  if (in_format == kInImg) {  // the stem from the image: 1x1 geometry over 5 patch groups, BN 64, epilogue 0
-    if (kh != 1 || kw != 1 || epilogue != 0 || block_n != 64 || in_groups != (kImgK * kImgK * kImgC + 31) / 32)
-      return OFLOW_E_MODE;
-    if ((long long)kImgC * 4 * H * W >= (1ll << 31)) return OFLOW_E_SHAPE;
-    a.ain = in_format;
-    if (d_addend) return OFLOW_E_MODE;
-    return dispatch_conv(a, kh, kw, block_n, epilogue, static_cast<hipStream_t>(stream));
-  }
-  if (in_format != kInF32 && (x_pixel_stride & 127)) return OFLOW_E_ALIGN;  // S32 / dense fp32: whole 128-B groups
-  if (in_format == kInF32Norm && x_pixel_stride != (long long)in_groups * 128) return OFLOW_E_SHAPE;  // dense [P][kg*32]
-  if (in_format == kInF32) {  // rows of cin fp32 channels, (kg - 1) * 32 < cin <= kg * 32, cin % 4 == 0
-    const long long cin = x_pixel_stride / 4;
-    if ((x_pixel_stride & 15) || cin > (long long)in_groups * 32 || cin <= (long long)(in_groups - 1) * 32) return OFLOW_E_SHAPE;
-    a.cin = static_cast<int>(cin);
-  }
-  if (in_format == kInF32Norm) {  // normalised + ReLU'd on load
-    if (!d_in_scale || !d_in_shift) return OFLOW_E_NULL;
-    if (kh != 3 || kw != 3 || epilogue != 0 || in_groups > kAinGroups) return OFLOW_E_MODE;
-    a.ia = d_in_scale;
-    a.ib = d_in_shift;
-  } else if (in_format == kInF32) {
-    if (kh != 1 || kw != 1 || epilogue != 0 || block_n != 128) return OFLOW_E_MODE;
-  }
-  a.ain = in_format;
-  if (d_addend) {  // GRU epilogues only; 16-B aligned rows of >= N floats
-    if (epilogue == 0) return OFLOW_E_MODE;
-    // the epilogue reads whole 8-float octets of every row: N a multiple of 8 keeps them inside the row
-    if (N % 8) return OFLOW_E_SHAPE;
-    if (((uintptr_t)d_addend & 15) || (addend_pixel_stride & 3) || addend_pixel_stride < N) return OFLOW_E_ALIGN;
-    a.add = d_addend;
-    a.addps = addend_pixel_stride;
-  }
-  if (d_ksplit_slab || d_ksplit_ctr) {
-    // split-K over the input groups: only the register-direct kernels (S32 input, fragment-major weights, multi-tap,
-    // 4-row tiles) take it; any other path this call would dispatch to runs unsplit (same results up to the order of
-    // one fp32 addition per output)
-    if (!d_ksplit_slab || !d_ksplit_ctr) return OFLOW_E_NULL;
-    if (((uintptr_t)d_ksplit_slab & 15) || ((uintptr_t)d_ksplit_ctr & 7)) return OFLOW_E_ALIGN;
-    if (ksplit_tiles <= 0) return OFLOW_E_SHAPE;
-    // (the register-direct instances: launch_bn / dispatch_conv -- 128-channel blocks of any multi-tap kernel but 2x2,
-    // 64- and 32-channel blocks of 3x3 ones; the GRU epilogues 1x5 / 5x1 only -- at the default tiles whatever the
-    // grid's size, see small_grid)
-    a.ks_slab = d_ksplit_slab;
-    const bool breg = in_format == kInS32 && a.wf != nullptr && use_breg(a, block_n, kh * kw) && kh * kw != 4 &&
-                      (block_n == 128 || (kh == 3 && kw == 3)) && (epilogue == 0 || kh * kw == 5);
-    a.ks_slab = nullptr;
-    if (breg && (in_groups % 2) == 0) {
-      // ksplit_tiles: the slab's capacity in (4 x 32-pixel tile, block_n channels) units of 128 * block_n floats
-      if ((long long)B * ((H + kTY - 1) / kTY) * ((W + kTX - 1) / kTX) * (n_pad / block_n) > ksplit_tiles)
-        return OFLOW_E_SHAPE;
-      a.ks_slab = d_ksplit_slab;
-      a.ks_ctr = d_ksplit_ctr;
-      a.ks_tiles = ksplit_tiles;
-      a.kg = in_groups / 2;
-      a.wbytes /= 2;
-    }
-  }
-  return dispatch_conv(a, kh, kw, block_n, epilogue, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int oflow_conv_s32_ex6(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack,
-                                  int n_pad, const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh,
-                                  int kw, int block_n, int epilogue, int activation, float out_scale, void* d_y0,
-                                  long long y0_pixel_stride, void* d_y1, long long y1_pixel_stride, float* d_f32,
-                                  long long f32_batch_stride, long long f32_channel_stride, int f32_accumulate,
-                                  float* d_gru_h, float* d_gru_z, int gru_channels, float* d_nhwc, int nhwc_pixel_stride,
-                                  float* d_stats, const void* d_res, long long res_pixel_stride, int res_activation,
-                                  int s2d, int in_format, const float* d_in_scale, const float* d_in_shift,
-                                  const float* d_addend, long long addend_pixel_stride, const void* d_wfrag,
-                                  float* d_ksplit_slab, unsigned* d_ksplit_ctr, long long ksplit_tiles,
-                                  const float* d_fh_weights, float* d_fh_partial, int fh_slabs, void* stream) {
-  if (epilogue != kEpiFlowHead)
-    return oflow_conv_s32_ex5(d_x, x_pixel_stride, in_groups, d_wpack, n_pad, d_wscale, d_bias, N, B, H, W, kh, kw,
-                              block_n, epilogue, activation, out_scale, d_y0, y0_pixel_stride, d_y1, y1_pixel_stride,
-                              d_f32, f32_batch_stride, f32_channel_stride, f32_accumulate, d_gru_h, d_gru_z,
-                              gru_channels, d_nhwc, nhwc_pixel_stride, d_stats, d_res, res_pixel_stride, res_activation,
-                              s2d, in_format, d_in_scale, d_in_shift, d_addend, addend_pixel_stride, d_wfrag,
-                              d_ksplit_slab, d_ksplit_ctr, ksplit_tiles, stream);
-  // the flow-head epilogue: 3x3 conv 32 * in_groups -> 256 on S32 input, ReLU; its only outputs are the partial sums
-  if (!d_fh_weights || !d_fh_partial) return OFLOW_E_NULL;
-  if (N != 256 || n_pad != 256 || fh_slabs != N / 64 || kh != 3 || kw != 3 || (block_n != 64 && block_n != 128))
-    return OFLOW_E_SHAPE;
-  if (in_format != kInS32 || activation != 1 || out_scale != 1.0f || d_y0 || d_y1 || d_f32 || d_gru_h || d_gru_z ||
-      d_nhwc || d_stats || d_res || s2d || d_addend || d_ksplit_slab || d_ksplit_ctr)
-    return OFLOW_E_MODE;
-  if ((x_pixel_stride & 127) || ((uintptr_t)d_fh_weights & 3) || ((uintptr_t)d_fh_partial & 3)) return OFLOW_E_ALIGN;
-  ConvArgs a;
-  // (the common checks of an epilogue-0 call writing one fp32 destination, which is then dropped)
-  const int st = build_conv_args(a, d_x, x_pixel_stride, in_groups, d_wpack, n_pad, d_wscale, d_bias, N, B, H, W, kh, kw,
-                                 block_n, 0, activation, out_scale, nullptr, 0, nullptr, 0, d_fh_partial, 0, 0, 0, nullptr,
-                                 nullptr, 0, nullptr, 0, nullptr, nullptr, 0, 0, 0);
-  if (st != OFLOW_OK) return st;
-  a.f = nullptr;
-  a.fhw = d_fh_weights;
-  a.fhy = d_fh_partial;
-  if (d_wfrag) {
-    if ((uintptr_t)d_wfrag & 15) return OFLOW_E_ALIGN;
-    a.wf = static_cast<const uint8_t*>(d_wfrag);
-  }
-  a.ain = kInS32;
-  return dispatch_conv(a, kh, kw, block_n, epilogue, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int oflow_conv_s32_ex3(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack,
-                                  int n_pad, const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh,
-                                  int kw, int block_n, int epilogue, int activation, float out_scale, void* d_y0,
-                                  long long y0_pixel_stride, void* d_y1, long long y1_pixel_stride, float* d_f32,
-                                  long long f32_batch_stride, long long f32_channel_stride, int f32_accumulate,
-                                  float* d_gru_h, float* d_gru_z, int gru_channels, float* d_nhwc, int nhwc_pixel_stride,
-                                  float* d_stats, const void* d_res, long long res_pixel_stride, int res_activation,
-                                  int s2d, int in_format, const float* d_in_scale, const float* d_in_shift,
-                                  const float* d_addend, long long addend_pixel_stride, void* stream) {
-  return oflow_conv_s32_ex4(d_x, x_pixel_stride, in_groups, d_wpack, n_pad, d_wscale, d_bias, N, B, H, W, kh, kw,
-                            block_n, epilogue, activation, out_scale, d_y0, y0_pixel_stride, d_y1, y1_pixel_stride,
-                            d_f32, f32_batch_stride, f32_channel_stride, f32_accumulate, d_gru_h, d_gru_z, gru_channels,
-                            d_nhwc, nhwc_pixel_stride, d_stats, d_res, res_pixel_stride, res_activation, s2d, in_format,
-                            d_in_scale, d_in_shift, d_addend, addend_pixel_stride, nullptr, stream);
-}
-
-extern "C" int oflow_conv_s32_ex2(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack,
-                                  int n_pad, const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh,
-                                  int kw, int block_n, int epilogue, int activation, float out_scale, void* d_y0,
-                                  long long y0_pixel_stride, void* d_y1, long long y1_pixel_stride, float* d_f32,
-                                  long long f32_batch_stride, long long f32_channel_stride, int f32_accumulate,
-                                  float* d_gru_h, float* d_gru_z, int gru_channels, float* d_nhwc, int nhwc_pixel_stride,
-                                  float* d_stats, const void* d_res, long long res_pixel_stride, int res_activation,
-                                  int s2d, int in_format, const float* d_in_scale, const float* d_in_shift,
-                                  void* stream) {
-  return oflow_conv_s32_ex3(d_x, x_pixel_stride, in_groups, d_wpack, n_pad, d_wscale, d_bias, N, B, H, W, kh, kw,
-                            block_n, epilogue, activation, out_scale, d_y0, y0_pixel_stride, d_y1, y1_pixel_stride,
-                            d_f32, f32_batch_stride, f32_channel_stride, f32_accumulate, d_gru_h, d_gru_z, gru_channels,
-                            d_nhwc, nhwc_pixel_stride, d_stats, d_res, res_pixel_stride, res_activation, s2d, in_format,
-                            d_in_scale, d_in_shift, nullptr, 0, stream);
-}
-
-extern "C" int oflow_conv_s32_ex(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack,
-                                 int n_pad, const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh,
-                                 int kw, int block_n, int epilogue, int activation, float out_scale, void* d_y0,
-                                 long long y0_pixel_stride, void* d_y1, long long y1_pixel_stride, float* d_f32,
-                                 long long f32_batch_stride, long long f32_channel_stride, int f32_accumulate,
-                                 float* d_gru_h, float* d_gru_z, int gru_channels, float* d_nhwc, int nhwc_pixel_stride,
-                                 float* d_stats, const void* d_res, long long res_pixel_stride, int res_activation,
-                                 int s2d, void* stream) {
-  return oflow_conv_s32_ex2(d_x, x_pixel_stride, in_groups, d_wpack, n_pad, d_wscale, d_bias, N, B, H, W, kh, kw,
-                            block_n, epilogue, activation, out_scale, d_y0, y0_pixel_stride, d_y1, y1_pixel_stride,
-                            d_f32, f32_batch_stride, f32_channel_stride, f32_accumulate, d_gru_h, d_gru_z, gru_channels,
-                            d_nhwc, nhwc_pixel_stride, d_stats, d_res, res_pixel_stride, res_activation, s2d, kInS32,
-                            nullptr, nullptr, stream);
-}
-
-extern "C" int oflow_conv_s32(const void* d_x, long long x_pixel_stride, int in_groups, const void* d_wpack, int n_pad,
-                              const float* d_wscale, const float* d_bias, int N, int B, int H, int W, int kh, int kw,
-                              int block_n, int epilogue, int activation, float out_scale, void* d_y0,
-                              long long y0_pixel_stride, void* d_y1, long long y1_pixel_stride, float* d_f32,
-                              long long f32_batch_stride, long long f32_channel_stride, int f32_accumulate,
-                              float* d_gru_h, float* d_gru_z, int gru_channels, void* stream) {
-  return oflow_conv_s32_ex(d_x, x_pixel_stride, in_groups, d_wpack, n_pad, d_wscale, d_bias, N, B, H, W, kh, kw,
-                           block_n, epilogue, activation, out_scale, d_y0, y0_pixel_stride, d_y1, y1_pixel_stride,
-                           d_f32, f32_batch_stride, f32_channel_stride, f32_accumulate, d_gru_h, d_gru_z, gru_channels,
-                           nullptr, 0, nullptr, nullptr, 0, 0, 0, stream);
+  return dispatch_conv(a, desc->kh, desc->kw, desc->block_n, desc->epilogue, static_cast<hipStream_t>(stream));
 }
 
 // experiment hook (not part of include/oflow.h): the small-grid pixel threshold, for in-process A/B runs (tools/exp)

@@ -225,7 +225,7 @@ class SplitEncoder:
 
     def _conv1(self, x, cw, shape):
         """A residual block's first conv -> relu(norm1(.)) as the second conv's input: with instance norm the raw
-        fp32 output and its statistics (normalised + ReLU'd while the next conv stages it, oflow_conv_s32_ex2); with
+        fp32 output and its statistics (normalised + ReLU'd while the next conv stages it, OFLOW_IN_F32_NORM); with
         folded batch norm an S32 tensor."""
         if self.inorm:
             raw, alpha, beta = self._conv_norm(x, cw, shape, "relu", raw_only=True)

@@ -74,7 +74,7 @@ for _bn in (CONV_BN, CONV_BN_SIDE):
 # r05: "tiled" = oflow_flow_head2_tiled_s32 (fp32 FMAs on an LDS-staged halo, 512 threads per 4 x 32 tile): step A/B
 # 18.81 vs 18.89 ms against "conv" (profiles/r05/s33_flow_head_tiled_ab.log; the first 256-thread form was 0.25 ms
 # slower, s32): the default until "fused"; two channel groups per staging pass: +0.6 % on the graph bench (s37), bit-identical
-# "fused" = the output conv folded into the flow head's first conv (oflow_conv_s32_ex6, OFLOW_EPI_FLOW_HEAD): conv1's
+# "fused" = the output conv folded into the flow head's first conv (oflow_conv_s32, OFLOW_EPI_FLOW_HEAD): conv1's
 # epilogue forms the 18 per-tap products per 64-channel slab from its fp32 tile and never writes the 256-channel
 # activation; oflow_flow_head_finish_f32 gathers them into coords1 and writes the next iteration's flow channels, so
 # flow_prep runs once per forward (11 kernels per lane iteration instead of 12). DESIGN.md §4 has the measurements.
@@ -83,7 +83,7 @@ FLOW_HEAD_MODE = _env_choice("OFLOW_FLOW_HEAD_MODE", "fused", ("fused", "tiled",
 # builds the patch operand in LDS) from this many pixels of the whole forward's batch up; below it flow_prep writes the
 # patch matrix and convf1 runs on the small-grid tiles. Bit-identical either way (same patch values, same k order).
 CONVF1_FROM_FLOW_MIN_PIXELS = 16384 if _env_choice("OFLOW_CONVF1_FROM_FLOW", "1", ("0", "1")) == "1" else 1 << 62  # (0: A/B)
-# r06: split-K (oflow_conv_s32_ex5) for the update convs whose lane launch fills fewer than half of the chip's
+# r06: split-K (oflow_conv_s32, KSplit) for the update convs whose lane launch fills fewer than half of the chip's
 # two-per-CU workgroup slots: the motion conv ("mo", 3x3 256 -> 126) and both GRU candidate convs ("q", 1x5 / 5x1
 # 256 -> 128) run 224 workgroups per 4-pair lane unsplit. Each tile's two workgroups sum half of the input groups and
 # meet through an fp32 slab (csrc/conv_s32.hip). Decided from the whole forward's pixel count (as the flow head's
@@ -441,7 +441,7 @@ class SplitUpdate:
             "fh2_f32": (fh.conv2.weight.detach().float().contiguous(), fh.conv2.bias.detach().float().contiguous()),
             # large grids: the same as fp32 FMAs on an LDS-staged halo (oflow_flow_head2_tiled_s32), repacked weights
             "fh2_tiled": (_native.flow_head2_tiled_weights(fh.conv2.weight), fh.conv2.bias.detach().float().contiguous()),
-            # large grids, "fused": [slab][channel][tap, output] for the flow-head epilogue of conv1 (oflow_conv_s32_ex6)
+            # large grids, "fused": [slab][channel][tap, output] for conv1's OFLOW_EPI_FLOW_HEAD epilogue
             "fh2_fused": _native.flow_head_fused_weights(fh.conv2.weight),
             "m1": CW(block.mask[0].weight, block.mask[0].bias, 256),
             "m2": CW(block.mask[2].weight, block.mask[2].bias, 576),

@@ -20,7 +20,7 @@ from . import _ops
 _LIB_PATH = os.environ.get(
     "OFLOW_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib", "liboflow_hip.so")
 )
-ABI_VERSION = 1
+ABI_VERSION = 2
 MAX_LEVELS = 8
 MAX_RADIUS = 7
 # grids below this many pixels run the flow head output conv as oflow_flow_head2_s32 (fp32 FMAs), larger ones as
@@ -52,12 +52,10 @@ SYMBOLS = (
     "oflow_conv_s32",
     "oflow_pack_s32_f32",
     "oflow_flow_prep_s32",
-    "oflow_conv_s32_ex",
     "oflow_stem_patches_s32",
     "oflow_norm_stats_finalize",
     "oflow_norm_apply_s32",
     "oflow_convex_upsample_f32",
-    "oflow_conv_s32_ex2",
     "oflow_corr_lookup_tiled_nhwc_f32",
     "oflow_corr_lookup_backward_f32",
     "oflow_corr_pyramid_grad_combine_f32",
@@ -68,9 +66,6 @@ SYMBOLS = (
     "oflow_corr_pyramid_tiled_s32",
     "oflow_flow_head2_s32",
     "oflow_flow_head2_tiled_s32",
-    "oflow_conv_s32_ex3",
-    "oflow_conv_s32_ex4",
-    "oflow_conv_s32_ex5",
     "oflow_normalize_images_f32",
     "oflow_replicate_pad_f32",
     "oflow_corr_fmap_grad_f32",
@@ -79,7 +74,6 @@ SYMBOLS = (
     "oflow_set_range_flag",
     "oflow_range_flag_exchange",
     "oflow_flow_head_col2im_f32",
-    "oflow_conv_s32_ex6",
     "oflow_flow_head_finish_f32",
     "oflow_timing_event_create",
     "oflow_timing_event_destroy",
@@ -92,6 +86,27 @@ SYMBOLS = (
     "oflow_corr_lookup_otf_backward_f32",
     "oflow_forward_interpolate_f32",
 )
+
+
+class ConvS32Desc(ctypes.Structure):
+    """oflow_conv_s32_desc (include/oflow.h), field for field in the header's order (tests/test_native_abi.py compares
+    the offsets with a C compiler's). Zero-filled = every optional feature off."""
+    _P, _I, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    _fields_ = [
+        ("struct_size", ctypes.c_uint),
+        ("in_format", _I), ("in_groups", _I), ("d_x", _P), ("x_pixel_stride", _L), ("d_in_scale", _P), ("d_in_shift", _P),
+        ("d_wpack", _P), ("d_wfrag", _P), ("d_wscale", _P), ("d_bias", _P), ("n_pad", _I), ("N", _I),
+        ("B", _I), ("H", _I), ("W", _I), ("kh", _I), ("kw", _I), ("block_n", _I),
+        ("epilogue", _I), ("activation", _I), ("out_scale", ctypes.c_float),
+        ("d_y0", _P), ("d_y1", _P), ("y0_pixel_stride", _L), ("y1_pixel_stride", _L),
+        ("d_f32", _P), ("f32_batch_stride", _L), ("f32_channel_stride", _L), ("f32_accumulate", _I),
+        ("d_gru_h", _P), ("d_gru_z", _P), ("gru_channels", _I),
+        ("d_nhwc", _P), ("d_stats", _P), ("d_res", _P), ("res_pixel_stride", _L),
+        ("nhwc_pixel_stride", _I), ("res_activation", _I), ("s2d", _I), ("d_addend", _P), ("addend_pixel_stride", _L),
+        ("d_ksplit_slab", _P), ("d_ksplit_ctr", _P), ("ksplit_tiles", _L),
+        ("d_fh_weights", _P), ("d_fh_partial", _P), ("fh_slabs", _I),
+    ]
+
 
 _lib = None
 _recorder = None  # optional {op name: [(start event, end event), ...]} filled around each launch
@@ -229,10 +244,7 @@ def load() -> ctypes.CDLL:
     lib.oflow_gru_blend_f32.restype = I
     lib.oflow_gru_blend_f32.argtypes = [P, L, P, P, L, P, P, L, I, I, I, P]
     lib.oflow_conv_s32.restype = I
-    lib.oflow_conv_s32.argtypes = [P, L, I, P, I, P, P, I, I, I, I, I, I, I, I, I, F, P, L, P, L, P, L, L, I, P, P, I, P]
-    lib.oflow_conv_s32_ex.restype = I
-    lib.oflow_conv_s32_ex.argtypes = [P, L, I, P, I, P, P, I, I, I, I, I, I, I, I, I, F, P, L, P, L, P, L, L, I, P, P, I,
-                                      P, I, P, P, L, I, I, P]
+    lib.oflow_conv_s32.argtypes = [ctypes.POINTER(ConvS32Desc), P]
     lib.oflow_stem_patches_s32.restype = I
     lib.oflow_stem_patches_s32.argtypes = [P, I, I, I, I, P, I, P]
     lib.oflow_norm_stats_finalize.restype = I
@@ -245,18 +257,10 @@ def load() -> ctypes.CDLL:
     lib.oflow_flow_prep_s32.argtypes = [P, I, I, I, P, P, L, P, L, P]
     lib.oflow_corr_lookup_otf_f16.restype = I
     lib.oflow_corr_lookup_otf_f16.argtypes = [P, PP, IP, IP, I, P, I, I, I, I, I, P, P]
-    lib.oflow_conv_s32_ex2.restype = I
-    lib.oflow_conv_s32_ex2.argtypes = list(lib.oflow_conv_s32_ex.argtypes[:-1]) + [I, P, P, P]
-    lib.oflow_conv_s32_ex3.restype = I
-    lib.oflow_conv_s32_ex3.argtypes = list(lib.oflow_conv_s32_ex2.argtypes[:-1]) + [P, L, P]
-    lib.oflow_conv_s32_ex4.restype = I
     lib.oflow_normalize_images_f32.restype = I
     lib.oflow_normalize_images_f32.argtypes = [P, P, L, P, P, P]
     lib.oflow_replicate_pad_f32.restype = I
     lib.oflow_replicate_pad_f32.argtypes = [P, P, I, L, I, I, I, I, I, I, P]
-    lib.oflow_conv_s32_ex4.argtypes = list(lib.oflow_conv_s32_ex3.argtypes[:-1]) + [P, P]
-    lib.oflow_conv_s32_ex5.restype = I
-    lib.oflow_conv_s32_ex5.argtypes = list(lib.oflow_conv_s32_ex4.argtypes[:-1]) + [P, P, L, P]
     lib.oflow_corr_lookup_backward_f32.restype = I
     lib.oflow_corr_lookup_backward_f32.argtypes = [P, P, I, I, I, I, PP, IP, IP, I, P]
     lib.oflow_corr_pyramid_grad_combine_f32.restype = I
@@ -293,8 +297,6 @@ def load() -> ctypes.CDLL:
     lib.oflow_timing_event_elapsed_ms.argtypes = [P, P, ctypes.POINTER(ctypes.c_float)]
     lib.oflow_flow_head_col2im_f32.restype = I
     lib.oflow_flow_head_col2im_f32.argtypes = [P, P, I, I, I, P, P]
-    lib.oflow_conv_s32_ex6.restype = I
-    lib.oflow_conv_s32_ex6.argtypes = list(lib.oflow_conv_s32_ex5.argtypes[:-1]) + [P, P, I, P]
     lib.oflow_flow_head_finish_f32.restype = I
     lib.oflow_flow_head_finish_f32.argtypes = [P, I, P, I, I, I, P, P, L, P, L, P]
     FP = ctypes.POINTER(F)
@@ -823,7 +825,7 @@ class S32Slice:
 
 class F32In:
     """Convolution input given as a dense fp32 NHWC tensor [B*H*W, C] (C % 4 == 0; the channels past C up to the next
-    multiple of 32 stage as zeros), split into hi + lo while the kernel stages it (oflow_conv_s32_ex2, OFLOW_IN_F32;
+    multiple of 32 stage as zeros), split into hi + lo while the kernel stages it (oflow_conv_s32, OFLOW_IN_F32;
     1x1 convs): the RAFT forward's lookup rows (corr_lookup_tiled_nhwc, C = L*(2r+1)^2 = 324)."""
 
     __slots__ = ("raw", "bhw")
@@ -917,7 +919,7 @@ class FlowIn:
 
 class NhwcNormIn:
     """Convolution input given as the previous convolution's raw fp32 NHWC output [B*H*W, C] plus its instance-norm
-    affine (scale, shift: [B, C]); the kernel stages relu(raw * scale + shift) (oflow_conv_s32_ex2), so the normalised
+    affine (scale, shift: [B, C]); the kernel stages relu(raw * scale + shift) (OFLOW_IN_F32_NORM), so the normalised
     activation is never written to HBM."""
 
     __slots__ = ("raw", "bhw", "scale", "shift")
@@ -1011,7 +1013,7 @@ class ConvWeights:
             self.frag()
 
     def frag(self) -> torch.Tensor:
-        """The pack reordered fragment-major for oflow_conv_s32_ex4's register-direct weights (include/oflow.h):
+        """The pack reordered fragment-major for oflow_conv_s32's register-direct weights (d_wfrag, include/oflow.h):
         [kg][t][n_pad][hi, lo][k 32] -> [kg][t][n / 32][sub-step][hi, lo][k half][n % 32][8], built once."""
         if self._frag is None:
             if self.layout != "conv" or self.n_pad % 32:
@@ -1080,7 +1082,7 @@ def conv_tiles(h: int, w: int) -> int:
 
 
 class KSplit:
-    """Split-K scratch for oflow_conv_s32_ex5 (include/oflow.h): an fp32 partial slab of ``tiles`` (4 x 32-pixel tile,
+    """Split-K scratch for oflow_conv_s32 (include/oflow.h): an fp32 partial slab of ``tiles`` (4 x 32-pixel tile,
     128-channel block) units and its [ticket, published] counters, zeroed here once. Calls sharing one KSplit must be
     stream-ordered (one per update lane)."""
 
@@ -1091,90 +1093,93 @@ class KSplit:
         self.ctr = torch.zeros(2 * self.tiles, device=device, dtype=torch.int32)
 
 
+def _conv_desc(x, cw: ConvWeights, block_n: int) -> ConvS32Desc:
+    """The fields every oflow_conv_s32 call sets; the rest stays zero (off) for the caller to fill by name."""
+    b, h, w = x.bhw
+    return ConvS32Desc(
+        struct_size=ctypes.sizeof(ConvS32Desc), in_format=getattr(x, "in_format", 0), in_groups=cw.kg, d_x=x.ptr,
+        x_pixel_stride=x.ps, d_wpack=cw.pack.data_ptr(), d_wscale=cw.wscale.data_ptr(),
+        d_bias=cw.bias.data_ptr() if cw.bias is not None else None, n_pad=cw.n_pad, N=cw.n, B=b, H=h, W=w, kh=cw.kh,
+        kw=cw.kw, block_n=int(block_n),
+    )
+
+
 def conv_s32(x: S32Slice, cw: ConvWeights, block_n: int, act: str = "none", out_scale: float = 1.0, y0=None, y1=None,
              f32=None, f32_accumulate: bool = False, epilogue: int = 0, gru_h=None, gru_z=None, nhwc=None, stats=None,
              res=None, res_act: str = "none", s2d: bool = False, addend=None, ksplit: "KSplit" = None) -> None:
-    """Split-fp16 convolution (oflow_conv_s32_ex5). x: input S32Slice with cw.kg groups, or NhwcNormIn (3x3 only). y0/y1: S32Slice destinations
-    (s2d: space-to-depth layout, half the spatial size). f32: (B, N', H, W) fp32 NCHW destination. nhwc: [P, N]
-    fp32 destination. stats: instance-norm partials [B, conv_tiles(H, W), n_pad, 3]. res: S32Slice residual added
-    after the activation, then res_act. epilogue 1/2: GRU gates / candidate with gru_h, gru_z ([P, CH] fp32);
+    """Split-fp16 convolution (oflow_conv_s32). x: input S32Slice with cw.kg groups, or NhwcNormIn (3x3 only). y0/y1:
+    S32Slice destinations (s2d: space-to-depth layout, half the spatial size). f32: (B, N', H, W) fp32 NCHW destination.
+    nhwc: [P, N] fp32 destination. stats: instance-norm partials [B, conv_tiles(H, W), n_pad, 3]. res: S32Slice residual
+    added after the activation, then res_act. epilogue 1/2: GRU gates / candidate with gru_h, gru_z ([P, CH] fp32);
     addend: fp32 [P, >= N] (row stride a multiple of 4, 16-B aligned) added before the gate activations (the GRU's
     hoisted context term). ksplit: split-K scratch (KSplit) -- the register-direct kernels then run each tile as two
-    workgroups over half the input groups each (one more fp32 addition per output); other kernels ignore it."""
+    workgroups over half the input groups each (the sum regrouped into two half-sums); other kernels ignore it."""
     what = "conv_s32"
     if CHECK_RANGE:
         _range_check(x, f"{what} {cw.kh}x{cw.kw}")
     if x.ng != cw.kg:
         raise RuntimeError(f"{what}: input has {x.ng} groups, weights expect {cw.kg}")
     b, h, w = x.bhw
-    nin = isinstance(x, NhwcNormIn)
-    in_format = getattr(x, "in_format", 0)
+    d = _conv_desc(x, cw, block_n)
+    d.epilogue, d.activation, d.res_activation, d.s2d = int(epilogue), ACT[act], ACT[res_act], int(bool(s2d))
+    d.out_scale = float(out_scale)
     hw_out = (h // 2, w // 2) if s2d else (h, w)
-    for d in (y0, y1):
-        if d is not None and (tuple(d.t.shape[:3]) != (b, *hw_out) or d.t.device != x.device):
+    for dst in (y0, y1):
+        if dst is not None and (tuple(dst.t.shape[:3]) != (b, *hw_out) or dst.t.device != x.device):
             raise RuntimeError(f"{what}: destination shape/device mismatch")
-    if res is not None and (tuple(res.t.shape[:3]) != (b, h, w) or res.ng * 32 < cw.n):
-        raise RuntimeError(f"{what}: residual shape mismatch")
-    fp, fbs, fcs = 0, 0, 0
+    if y0 is not None:
+        d.d_y0, d.y0_pixel_stride = y0.ptr, y0.ps
+    if y1 is not None:
+        d.d_y1, d.y1_pixel_stride = y1.ptr, y1.ps
+    if res is not None:
+        if tuple(res.t.shape[:3]) != (b, h, w) or res.ng * 32 < cw.n:
+            raise RuntimeError(f"{what}: residual shape mismatch")
+        d.d_res, d.res_pixel_stride = res.ptr, res.ps
     if f32 is not None:
         if f32.dtype != torch.float32 or f32.dim() != 4 or tuple(f32.shape[2:]) != (h, w) or f32.shape[0] != b:
             raise RuntimeError(f"{what}: fp32 destination must be (B, C, H, W) fp32")
         if f32.stride(3) != 1 or f32.stride(2) != w or f32.shape[1] < cw.n and epilogue == 0:
             raise RuntimeError(f"{what}: fp32 destination planes must be contiguous with >= N channels")
-        fp, fbs, fcs = f32.data_ptr(), f32.stride(0), f32.stride(1)
-    if nhwc is not None and (nhwc.dtype != torch.float32 or not nhwc.is_contiguous() or nhwc.numel() != b * h * w * cw.n):
-        raise RuntimeError(f"{what}: nhwc destination must be contiguous fp32 [P, {cw.n}]")
-    if stats is not None and (stats.dtype != torch.float32 or stats.numel() < b * conv_tiles(h, w) * cw.n_pad * 3):
-        raise RuntimeError(f"{what}: stats partials buffer too small")
-    gh = gz = 0
-    gch = 0
+        d.d_f32, d.f32_batch_stride, d.f32_channel_stride = f32.data_ptr(), f32.stride(0), f32.stride(1)
+        d.f32_accumulate = int(bool(f32_accumulate))
+    if nhwc is not None:
+        if nhwc.dtype != torch.float32 or not nhwc.is_contiguous() or nhwc.numel() != b * h * w * cw.n:
+            raise RuntimeError(f"{what}: nhwc destination must be contiguous fp32 [P, {cw.n}]")
+        d.d_nhwc, d.nhwc_pixel_stride = nhwc.data_ptr(), cw.n
+    if stats is not None:
+        if stats.dtype != torch.float32 or stats.numel() < b * conv_tiles(h, w) * cw.n_pad * 3:
+            raise RuntimeError(f"{what}: stats partials buffer too small")
+        d.d_stats = stats.data_ptr()
     if epilogue:
         gch = cw.n // 2 if epilogue == 1 else cw.n
         for tt in (gru_h, gru_z):
             if tt is None or tt.dtype != torch.float32 or not tt.is_contiguous() or tt.numel() != b * h * w * gch:
                 raise RuntimeError(f"{what}: GRU state tensors must be contiguous fp32 [P, {gch}]")
-        gh, gz = gru_h.data_ptr(), gru_z.data_ptr()
-    ap, aps = 0, 0
+        d.d_gru_h, d.d_gru_z, d.gru_channels = gru_h.data_ptr(), gru_z.data_ptr(), gch
     if addend is not None:
         if (not epilogue or addend.dtype != torch.float32 or addend.dim() != 2 or addend.stride(1) != 1
                 or addend.shape[0] != b * h * w or addend.shape[1] < cw.n or addend.stride(0) % 4
                 or addend.data_ptr() % 16 or addend.device != x.device):
             raise RuntimeError(f"{what}: addend must be a GRU-epilogue fp32 [P, >= {cw.n}] view with 16-B aligned rows")
-        ap, aps = addend.data_ptr(), addend.stride(0)
-    dev = x.device
+        d.d_addend, d.addend_pixel_stride = addend.data_ptr(), addend.stride(0)
+    if d.in_format == NhwcNormIn.in_format:
+        d.d_in_scale, d.d_in_shift = x.scale.data_ptr(), x.shift.data_ptr()
     # register-direct weights for the 128- (and, CONV_BREG64, 64-) channel blocks of multi-tap convs on S32 input (the
-    # kernel ignores wf elsewhere)
-    wf = (cw.frag().data_ptr() if CONV_BREG and (int(block_n) == 128 or (CONV_BREG64 and int(block_n) == 64)
-                                                 or (CONV_BREG32 and int(block_n) == 32))
-          and cw.kh * cw.kw > 1 and not nin
-          and in_format == 0 and cw.layout == "conv" else None)
+    # kernel ignores d_wfrag elsewhere)
+    if (CONV_BREG and (d.block_n == 128 or (CONV_BREG64 and d.block_n == 64) or (CONV_BREG32 and d.block_n == 32))
+            and cw.kh * cw.kw > 1 and d.in_format == 0 and cw.layout == "conv"):
+        d.d_wfrag = cw.frag().data_ptr()
     if _flops is not None:
         taps, p_out = cw.kh * cw.kw, b * h * w  # (s2d only changes where the epilogue writes)
-        n_exec = -(-cw.n_pad // int(block_n)) * int(block_n)
+        n_exec = -(-cw.n_pad // d.block_n) * d.block_n
         _count(3 * 2 * p_out * n_exec * cw.kg * 32 * taps, 2 * p_out * cw.n * cw.cin * taps)
-    ks_slab = ks_ctr = None
-    ks_tiles = 0
-    if ksplit is not None and wf is not None:
-        if ksplit.slab.device != dev or ksplit.block_n < int(block_n):
+    if ksplit is not None and d.d_wfrag is not None:
+        if ksplit.slab.device != x.device or ksplit.block_n < d.block_n:
             raise RuntimeError(f"{what}: split-K scratch on another device or for narrower channel blocks")
-        ks_slab, ks_ctr = ksplit.slab.data_ptr(), ksplit.ctr.data_ptr()
-        ks_tiles = ksplit.tiles * (ksplit.block_n // int(block_n))
-    with torch.cuda.device(dev), _Timed(f"conv{cw.kh}x{cw.kw}", dev):
-        _check(
-            load().oflow_conv_s32_ex5(
-                x.ptr, x.ps, cw.kg, cw.pack.data_ptr(), cw.n_pad, cw.wscale.data_ptr(),
-                cw.bias.data_ptr() if cw.bias is not None else None, cw.n, b, h, w, cw.kh, cw.kw, int(block_n),
-                int(epilogue), ACT[act], float(out_scale), y0.ptr if y0 is not None else None, y0.ps if y0 is not None else 0,
-                y1.ptr if y1 is not None else None, y1.ps if y1 is not None else 0, fp or None, fbs, fcs,
-                int(bool(f32_accumulate)), gh or None, gz or None, gch,
-                nhwc.data_ptr() if nhwc is not None else None, cw.n,
-                stats.data_ptr() if stats is not None else None,
-                res.ptr if res is not None else None, res.ps if res is not None else 0, ACT[res_act], int(bool(s2d)),
-                in_format, x.scale.data_ptr() if nin else None, x.shift.data_ptr() if nin else None,
-                ap or None, aps, wf, ks_slab, ks_ctr, ks_tiles, _stream(dev),
-            ),
-            what,
-        )
+        d.d_ksplit_slab, d.d_ksplit_ctr = ksplit.slab.data_ptr(), ksplit.ctr.data_ptr()
+        d.ksplit_tiles = ksplit.tiles * (ksplit.block_n // d.block_n)
+    with torch.cuda.device(x.device), _Timed(f"conv{cw.kh}x{cw.kw}", x.device):
+        _check(load().oflow_conv_s32(ctypes.byref(d), _stream(x.device)), what)
 
 
 def flow_head2(x: "S32Slice", weight: torch.Tensor, bias: torch.Tensor, coords: torch.Tensor) -> None:
@@ -1241,12 +1246,12 @@ def flow_head_col2im(y: torch.Tensor, bias: torch.Tensor, coords: torch.Tensor) 
                                                  _stream(coords.device)), what)
 
 
-FLOW_HEAD_SLABS = 4  # 64-channel slabs of the flow head's 256 hidden channels (oflow_conv_s32_ex6)
+FLOW_HEAD_SLABS = 4  # 64-channel slabs of the flow head's 256 hidden channels (OFLOW_EPI_FLOW_HEAD)
 
 
 def flow_head_fused_weights(weight: torch.Tensor) -> torch.Tensor:
     """The flow head's output conv weight (2, 256, 3, 3) -> the [slab 4][channel 64][t*2 + c] fp32 copy the flow-head
-    epilogue reads (oflow_conv_s32_ex6), t = ky*3 + kx."""
+    epilogue reads (OFLOW_EPI_FLOW_HEAD), t = ky*3 + kx."""
     if tuple(weight.shape) != (2, 64 * FLOW_HEAD_SLABS, 3, 3):
         raise RuntimeError(f"flow_head_fused_weights: weight must be (2, {64 * FLOW_HEAD_SLABS}, 3, 3)")
     return weight.detach().float().permute(1, 2, 3, 0).reshape(FLOW_HEAD_SLABS, 64, 18).contiguous()
@@ -1259,7 +1264,7 @@ def flow_head_partial_empty(b: int, h: int, w: int, device) -> torch.Tensor:
 
 def conv_s32_flow_head(x: "S32Slice", cw: "ConvWeights", block_n: int, w2r: torch.Tensor, partial) -> None:
     """The flow head's first conv (3x3 -> 256, ReLU) with the 256 -> 2 output conv's per-tap products formed in its
-    epilogue (oflow_conv_s32_ex6, OFLOW_EPI_FLOW_HEAD): writes ``partial`` [4, B, 18, H, W] and nothing else;
+    epilogue (oflow_conv_s32, OFLOW_EPI_FLOW_HEAD): writes ``partial`` [4, B, 18, H, W] and nothing else;
     ``flow_head_finish`` completes coords1 += conv2(relu(conv1(x))). cw: conv1's ConvWeights; w2r:
     flow_head_fused_weights(conv2.weight); block_n 64 (LDS-staged weights) or 128 (register-direct)."""
     what = "conv_s32_flow_head"
@@ -1269,30 +1274,25 @@ def conv_s32_flow_head(x: "S32Slice", cw: "ConvWeights", block_n: int, w2r: torc
     dev = x.device
     if (w2r.dtype != torch.float32 or not w2r.is_contiguous() or tuple(w2r.shape[1:]) != (64, 18) or w2r.device != dev):
         raise RuntimeError(f"{what}: w2r must be flow_head_fused_weights(conv2.weight) on the input's device")
-    slabs, pp = 0, None
+    d = _conv_desc(x, cw, block_n)
+    d.epilogue, d.activation, d.out_scale = 3, ACT["relu"], 1.0  # OFLOW_EPI_FLOW_HEAD
+    d.d_fh_weights = w2r.data_ptr()
     if partial is not None:
         if (partial.dtype != torch.float32 or not partial.is_contiguous() or partial.dim() != 5
                 or tuple(partial.shape[1:]) != (b, 18, h, w) or partial.device != dev):
             raise RuntimeError(f"{what}: partial must be contiguous fp32 (slabs, {b}, 18, {h}, {w}) on the input's device")
-        slabs, pp = int(partial.shape[0]), partial.data_ptr()
+        d.fh_slabs, d.d_fh_partial = int(partial.shape[0]), partial.data_ptr()
     if w2r.shape[0] != FLOW_HEAD_SLABS:
-        slabs = -1  # (a weight copy of another slab count: the entry reports the shape error)
-    wf = cw.frag().data_ptr() if int(block_n) == 128 and cw.layout == "conv" else None
+        d.fh_slabs = -1  # (a weight copy of another slab count: the entry reports the shape error)
+    if d.block_n == 128 and cw.layout == "conv":
+        d.d_wfrag = cw.frag().data_ptr()
     if _flops is not None:
-        n_exec = -(-cw.n_pad // int(block_n)) * int(block_n)
+        n_exec = -(-cw.n_pad // d.block_n) * d.block_n
         _count(3 * 2 * b * h * w * n_exec * cw.kg * 32 * 9, 2 * b * h * w * cw.n * cw.cin * 9)
         fl = 2 * b * h * w * 2 * cw.n * 9
         _count(0, fl, fl)
     with torch.cuda.device(dev), _Timed("conv3x3", dev):
-        _check(
-            load().oflow_conv_s32_ex6(
-                x.ptr, x.ps, cw.kg, cw.pack.data_ptr(), cw.n_pad, cw.wscale.data_ptr(),
-                cw.bias.data_ptr() if cw.bias is not None else None, cw.n, b, h, w, cw.kh, cw.kw, int(block_n),
-                3, ACT["relu"], 1.0, None, 0, None, 0, None, 0, 0, 0, None, None, 0, None, cw.n, None, None, 0, 0, 0,
-                0, None, None, None, 0, wf, None, None, 0, w2r.data_ptr(), pp, slabs, _stream(dev),
-            ),
-            what,
-        )
+        _check(load().oflow_conv_s32(ctypes.byref(d), _stream(dev)), what)
 
 
 def flow_head_finish(partial: torch.Tensor, bias: torch.Tensor, coords: torch.Tensor, flow0=None, flow1=None) -> None:
