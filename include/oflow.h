@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define OFLOW_ABI_VERSION 2
+#define OFLOW_ABI_VERSION 3
 
 #define OFLOW_OK 0
 #define OFLOW_E_NULL (-1)      /* a required pointer is NULL */
@@ -292,25 +292,6 @@ typedef struct oflow_conv_s32_desc {
    * (update.py:92-105) run over [h | motion | flow] only. */
   const float* d_addend;
   long long addend_pixel_stride;
-  /* Split-K over the input groups for the register-direct kernels (S32 input, d_wfrag given, in_groups even; a 4-pair
-   * lane's GRU q / motion convs fill 224 of 512 two-per-CU slots unsplit). Each 4 x 32-pixel tile (x block_n channels)
-   * runs as two workgroups, each summing half of the input groups; the first to finish hands its fp32 partials to the
-   * second through d_ksplit_slab (write-through stores, an agent-scope counter, an acquire on the reader), which adds
-   * them and runs the epilogue. The split regroups the whole reduction over the input groups -- each output is the sum
-   * of two half-sums, not one running sum -- so it is not bit-identical to the unsplit call: both lie within the conv's
-   * float64 bound, 2e-6 * conv(|x|, |w|) + 1e-6, of the exact result and of each other (asserted by
-   * tests/test_gpu_conv_ksplit.py). The result does not depend on which workgroup finishes first.
-   *   d_ksplit_slab: >= ksplit_tiles * 128 * block_n floats, 16-B aligned, any contents;
-   *   d_ksplit_ctr : 2 * ksplit_tiles uint32, 8-B aligned, ZEROED ONCE before the first call; the counters only grow
-   *     (two tickets and one publication per tile and call), so successive calls and graph replays need no reset -- but
-   *     calls that share a buffer pair must be stream-ordered (never in flight together);
-   *   ksplit_tiles : capacity; OFLOW_E_SHAPE if the call needs B * ceil(H/4) * ceil(W/32) * n_pad / block_n more.
-   * A split call always runs the default 4-row tiles, small grids included (so that a caller deciding the split from
-   * its whole batch gets the same bits from any partition of it into calls); calls of other shapes (not
-   * register-direct, odd in_groups) run unsplit. Both pointers NULL: no split. */
-  float* d_ksplit_slab;
-  unsigned int* d_ksplit_ctr;
-  long long ksplit_tiles;
   /* Flow head (epilogue OFLOW_EPI_FLOW_HEAD): update.py:31-37, conv2(relu(conv1(x))), with its 256 -> 2 output conv
    * folded into conv1's epilogue. The call is conv1 (3x3, S32 input, N = n_pad = 256, activation 1 = ReLU, out_scale 1,
    * block_n 64 or 128; 128 needs d_wfrag); relu(conv1) is never stored. Per pixel and 64-channel slab the epilogue
@@ -322,18 +303,14 @@ typedef struct oflow_conv_s32_desc {
    * so every block_n and weight staging gives the same bits. oflow_flow_head_finish_f32 gathers the taps and slabs.
    *   d_fh_weights: conv2's weight (2, 256, 3, 3) repacked [slab 4][channel 64][t*2 + c] fp32;
    *   fh_slabs    : N / 64 = 4 (else OFLOW_E_SHAPE).
-   * Every destination of the other epilogues, d_addend and the split-K buffers must be NULL (OFLOW_E_MODE). Always the
-   * default 4 x 32 tiles, small grids included. Any other epilogue ignores these three fields. */
+   * Every destination of the other epilogues and d_addend must be NULL (OFLOW_E_MODE). Always the default 4 x 32 tiles,
+   * small grids included. Any other epilogue ignores these three fields. */
   const float* d_fh_weights;
   float* d_fh_partial;
   int fh_slabs;
 } oflow_conv_s32_desc;
 int oflow_conv_s32(const oflow_conv_s32_desc* desc, void* stream);
 
-/* oflow_flow_head2_s32: the flow head's output conv (update.py:35-36 conv2: 3x3, C -> 2, zero padding) added into
- * coords (B, 2, H, W) fp32 in place (raft.py:133 `coords1 = coords1 + delta_flow`), from an S32 input of in_groups
- * groups (1..8): fp32 FMAs on the exact S32 values; d_weight (2, C, 3, 3) fp32 as the nn.Conv2d stores it, d_bias [2].
- * Built for small grids (one image at 1/8 resolution); larger ones run faster as oflow_conv_s32 with n_pad 32. */
 /* oflow_flow_head_col2im_f32: d_coords (B, 2, H, W) += d_bias[c] + sum_{ky,kx} d_y[b][(ky*3+kx)*2 + c][y+ky-1][x+kx-1]
  * (zero outside the image): the flow head's output conv (update.py:35-36, conv2 3x3 C -> 2, raft.py:133 coords1 +=
  * delta_flow) as a 1x1 conv C -> 18 per-tap products (oflow_conv_s32 with an fp32 NCHW destination d_y (B, 18, H, W))
@@ -384,6 +361,10 @@ int oflow_timing_event_destroy(void* ev);
 int oflow_timing_event_record(void* ev, void* stream, int external);
 int oflow_timing_event_elapsed_ms(void* start, void* end, float* ms);
 
+/* oflow_flow_head2_s32: the flow head's output conv (update.py:35-36 conv2: 3x3, C -> 2, zero padding) added into
+ * coords (B, 2, H, W) fp32 in place (raft.py:133 `coords1 = coords1 + delta_flow`), from an S32 input of in_groups
+ * groups (1..8): fp32 FMAs on the exact S32 values; d_weight (2, C, 3, 3) fp32 as the nn.Conv2d stores it, d_bias [2].
+ * Built for small grids (one image at 1/8 resolution); larger ones run faster as oflow_conv_s32 with n_pad 32. */
 int oflow_flow_head2_s32(const void* d_x, long long x_pixel_stride, int in_groups, const float* d_weight,
                          const float* d_bias, int B, int H, int W, float* d_coords, void* stream);
 /* oflow_flow_head2_tiled_s32: oflow_flow_head2_s32 for large grids (update.py:36 FlowHead.conv2 + raft.py:133): each

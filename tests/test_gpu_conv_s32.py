@@ -505,8 +505,6 @@ def test_flow_head_col2im_matches_fp64_and_conv(b, h, w):
     """The flow head's output conv (update.py:36, 3x3 256 -> 2, bias; raft.py:133 coords1 += delta) as a 1x1 conv
     256 -> 18 (per-tap products) + oflow_flow_head_col2im_f32, against float64 F.conv2d of the same split operands, and
     against the 3x3 conv_s32 path (fp32 reordering apart): borders (zero padding), a 1x1 grid, KITTI's 47x156."""
-    from model.update import SplitUpdate  # noqa: F401  (the weight layout under test is SplitUpdate's "fh2T")
-
     g = torch.Generator().manual_seed(b * 1000 + h + w)
     x = torch.relu(torch.randn(b, 256, h, w, generator=g) * 2.0).to(DEV)
     wt = (torch.randn(2, 256, 3, 3, generator=g) / math.sqrt(256 * 9)).to(DEV)

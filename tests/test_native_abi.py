@@ -27,6 +27,17 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
 
 
+def test_split_k_is_gone():
+    """Split-K (the ABI version 2 descriptor fields; it never had an exported symbol of its own) is in neither the
+    header nor the binding, and a descriptor of the version 2 size is refused."""
+    text = open(os.path.join(REPO, "include", "oflow.h")).read()
+    assert "ksplit" not in text.lower() and "split-k" not in text.lower()
+    assert not [n for n, _ in _native.ConvS32Desc._fields_ if "ksplit" in n] and not hasattr(_native, "KSplit")
+    d = _native.ConvS32Desc()
+    d.struct_size = ctypes.sizeof(_native.ConvS32Desc) + 24  # the three version 2 fields more
+    assert _native.load().oflow_conv_s32(ctypes.byref(d), None) == MODE
+
+
 def test_abi_version_and_status_strings():
     lib = _native.load()
     assert lib.oflow_abi_version() == _native.ABI_VERSION
@@ -91,12 +102,12 @@ def test_conv_desc_layout_matches_the_header(tmp_path):
     out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
     assert int(out.pop("sizeof")) == ctypes.sizeof(Desc)
     assert {n: int(v) for n, v in out.items()} == {n: getattr(Desc, n).offset for n in names}
-    # every member the header declares is mirrored (47 + struct_size), so none can hide in padding
+    # every member the header declares is mirrored (44 + struct_size), so none can hide in padding
     text = open(os.path.join(REPO, "include", "oflow.h")).read()
     body = text[text.index("typedef struct oflow_conv_s32_desc {"):text.index("} oflow_conv_s32_desc;")]
     decls = re.sub(r"/\*.*?\*/", "", body, flags=re.S).split("{", 1)[1]
     declared = [m for stmt in decls.split(";") for m in re.findall(r"\**(\w+)\s*(?:,|$)", stmt.strip())]
-    assert declared == names and len(names) == 48
+    assert declared == names and len(names) == 45
 
 
 # one valid call per family; each case below changes a few fields of one of them
@@ -104,7 +115,6 @@ BASE = dict(d_x=A, x_pixel_stride=8 * 128, in_groups=8, d_wpack=A, n_pad=128, d_
             block_n=128, epilogue=0, activation=0, out_scale=1.0, d_f32=A)
 GRU = dict(kh=1, kw=5, epilogue=1, d_f32=None, d_y0=A, y0_pixel_stride=256, d_gru_h=A, d_gru_z=A, gru_channels=64)
 FH = dict(epilogue=3, N=256, n_pad=256, block_n=64, activation=1, d_f32=None, d_fh_weights=A, d_fh_partial=A, fh_slabs=4)
-KS = dict(d_wfrag=A, d_ksplit_slab=A, d_ksplit_ctr=A, ksplit_tiles=64)
 # The expected statuses are what the last positional entry point (ABI version 1) returned for the same arguments
 # (recorded from that library; every case fails a check, or finds no kernel, before a launch).
 STATUS_CASES = [
@@ -116,7 +126,6 @@ STATUS_CASES = [
     ("epilogue 1 without GRU pointers", dict(kh=1, kw=5, epilogue=1), NULL),
     ("d_addend with epilogue 0", dict(d_addend=A, addend_pixel_stride=128), MODE),
     ("in_format 5", dict(in_format=5), MODE),
-    ("split-K slab without counters", dict(KS, d_ksplit_ctr=None), NULL),
     ("7x7 kernel", dict(kh=7, kw=7), SHAPE),
     ("flow head with d_y0", dict(FH, d_y0=A, y0_pixel_stride=1024), MODE),
     ("flow head with fh_slabs 3", dict(FH, fh_slabs=3), SHAPE),
@@ -158,12 +167,6 @@ STATUS_CASES = [
      dict(in_format=3, in_groups=5, block_n=64, kh=1, kw=1, d_addend=A, addend_pixel_stride=128), MODE),
     ("OFLOW_IN_FLOW7 with 5 groups", dict(in_format=4, in_groups=5, kh=1, kw=1), MODE),
     ("OFLOW_IN_FLOW7 with d_addend", dict(in_format=4, in_groups=4, kh=1, kw=1, d_addend=A, addend_pixel_stride=128), SHAPE),
-    ("split-K counters without slab", dict(KS, d_ksplit_slab=None), NULL),
-    ("split-K misaligned slab", dict(KS, d_ksplit_slab=A + 4), ALIGN),
-    ("split-K misaligned counters", dict(KS, d_ksplit_ctr=A + 4), ALIGN),
-    ("split-K ksplit_tiles 0", dict(KS, ksplit_tiles=0), SHAPE),
-    ("split-K slab too small", dict(KS, B=2, ksplit_tiles=1), SHAPE),
-    ("split-K with a 7x7 kernel", dict(KS, kh=7, kw=7), SHAPE),
     ("flow head without d_fh_partial", dict(FH, d_fh_partial=None), NULL),
     ("flow head with N 128", dict(FH, N=128), SHAPE),
     ("flow head with a 1x5 kernel", dict(FH, kh=1, kw=5), SHAPE),
@@ -174,7 +177,6 @@ STATUS_CASES = [
     ("flow head with d_f32", dict(FH, d_f32=A), MODE),
     ("flow head with s2d", dict(FH, s2d=1), MODE),
     ("flow head with d_addend", dict(FH, d_addend=A, addend_pixel_stride=256), MODE),
-    ("flow head with split-K buffers", dict(FH, **KS), MODE),
     ("flow head with x_pixel_stride 16 mod 128", dict(FH, x_pixel_stride=1040), ALIGN),
     ("flow head with misaligned d_fh_partial", dict(FH, d_fh_partial=A + 2), ALIGN),
     ("flow head with d_x NULL", dict(FH, d_x=None), NULL),
@@ -191,8 +193,6 @@ STATUS_CASES = [
     ("weights of 2 GiB and misaligned d_wfrag", dict(in_groups=14564, d_wfrag=A + 8), SHAPE),
     ("misaligned d_wfrag and in_format 5", dict(d_wfrag=A + 8, in_format=5), ALIGN),
     ("in_format 5 and d_addend with epilogue 0", dict(in_format=5, d_addend=A, addend_pixel_stride=128), MODE),
-    ("d_addend with epilogue 0 and split-K slab without counters",
-     dict(KS, d_ksplit_ctr=None, d_addend=A, addend_pixel_stride=128), MODE),
     ("epilogue 4 with the flow-head pointers", dict(FH, epilogue=4), MODE),
     ("GRU without pointers and misaligned d_x", dict(kh=1, kw=5, epilogue=1, d_x=A + 8), ALIGN),
     ("GRU with N != 2 * gru_channels and d_stats", dict(GRU, gru_channels=128, d_stats=A), SHAPE),

@@ -3,7 +3,7 @@ from a HIP graph as bench.py --graph does): one GraphedRAFT per variant, each ca
 then replays alternated variant by variant for ROUNDS rounds (median ms per step per variant). Flows are compared with
 the first variant's.
 
-    VARIANTS='off:update.KSPLIT_LAYERS=frozenset();on:update.KSPLIT_LAYERS=frozenset({"mo","q"})' \
+    VARIANTS='fused:update.FLOW_HEAD_MODE="fused";tiled:update.FLOW_HEAD_MODE="tiled"' \
         python tools/exp/run_graph_ab.py
 Each variant is "name:module.ATTR=python-expression[,,module.ATTR=...]" over the modules of methods/raft/model, or
 "lib.oflow_exp_set_X=V/R": liboflow's int experiment setter, V during the capture, R after it."""

@@ -120,11 +120,6 @@ struct ConvArgs {
   int wbytes;              // bytes of the packed weights (kg * taps * npad * 128)
   const uint8_t* wf;       // the same weights fragment-major (register-direct B, BREG kernels), or null
   int exp_flags;           // experiments only (oflow_exp_set_conv_flags): bit 0 = the stem's element-wise window loop
-  // split-K (BREG kernels only, d_ksplit_slab / d_ksplit_ctr): gridDim.z = 2 workgroups per tile, each summing half of the input
-  // groups (kg above is the half); per tile a BM x BN fp32 partial slab and two counters [ticket, published]
-  float* ks_slab;
-  unsigned* ks_ctr;
-  long long ks_tiles;      // tiles (x channel blocks) the slab and counters hold
   // flow-head epilogue (EPI 3, OFLOW_EPI_FLOW_HEAD): the output conv's weights [slab][64][18] and the per-tap partial
   // sums [slabs][B][18][H][W] (fp32)
   const float* fhw;
@@ -346,13 +341,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   const int r = lane & 31, hh = lane >> 5;
-  if constexpr (BREG) {
-    if (a.ks_slab != nullptr) {  // split-K: this workgroup's half of the input groups (a.kg is the half count)
-      const int z = blockIdx.z;
-      a.x += (long long)z * a.kg * 128;                 // S32 channel slice: + 128 B per group
-      a.wf += (long long)z * a.kg * T * a.npad * 128;   // fragment-major weights are step-major, step = (group, tap)
-    }
-  }
   auto aswz = [](int p) { return (BREG || OFLOW_PAD_ROWS) ? 0 : swz(p); };  // row slot swizzles (none with padded rows)
   auto bswz = [](int n) { return OFLOW_PAD_ROWS ? 0 : swz(n); };
 
@@ -833,71 +821,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
 #undef OFLOW_LOAD_B
 #undef OFLOW_WRITE_B
 
-  if constexpr (BREG) {
-    if (a.ks_slab != nullptr) {
-      // Split-K hand-off (MI355X_MICROARCH.md "inter-workgroup visibility"; cdna_hip_programming.md Guideline 16 R1):
-      // the tile's two workgroups take tickets from one counter; the first publishes its partial sums write-through
-      // (16-B sc1 stores: no release fence), drains them, and one lane bumps the tile's "published" counter; the second
-      // polls that counter (relaxed agent-scope loads), drops its L1 with one agent acquire and adds the partials to its
-      // own before running the epilogue. fp32 addition is commutative, so acc_0 + acc_1 is the same bits whichever
-      // workgroup arrives second. Counters only grow (two tickets and one publication per tile and launch), so they
-      // need no reset between launches or graph replays; the host zeroes them once. The second arriver polls only after
-      // the first took its ticket (it is resident and past its main loop): no dependence on dispatch order. The poll is
-      // bounded (a hang would hold the GPU): past the bound it proceeds without the partials (the results are then
-      // wrong, which the parity tests see).
-      typedef __attribute__((address_space(1))) unsigned gu32;
-      __shared__ unsigned sTicket;
-      const int tile_id = blockIdx.y * gridDim.x + blockIdx.x;
-      gu32* ctr = (gu32*)(a.ks_ctr) + 2 * tile_id;  // (global address space: no flat atomics)
-      if (tid == 0) sTicket = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __syncthreads();
-      const unsigned ticket = sTicket;
-      // slab of the tile: [wave][mt][nt][16-B quarter of the accumulator][lane 64][16 B] (one wave instruction = 1 KB)
-      const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc(
-          a.ks_slab + (size_t)tile_id * (BM * BN), (short)0, BM * BN * 4, 0x00020000);
-      const int sbase = wave * (MT * NT * 4096) + lane * 16;
-      if ((ticket & 1u) == 0u) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int e4 = 0; e4 < 4; ++e4) {
-              const u32x4 v = {__float_as_uint(acc[mt][nt][4 * e4]), __float_as_uint(acc[mt][nt][4 * e4 + 1]),
-                               __float_as_uint(acc[mt][nt][4 * e4 + 2]), __float_as_uint(acc[mt][nt][4 * e4 + 3])};
-              __builtin_amdgcn_raw_buffer_store_b128(v, rsS, sbase + ((mt * NT + nt) * 4 + e4) * 1024, 0, 16);  // sc1
-            }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its write-through stores
-        __syncthreads();
-        if (tid == 0) __hip_atomic_fetch_add(ctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-      }
-      if (tid == 0) {
-        const unsigned want = (ticket >> 1) + 1u;
-        for (unsigned spin = 0; spin < (1u << 24); ++spin) {
-          if (static_cast<int>(__hip_atomic_load(ctr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) >= 0) break;
-          __builtin_amdgcn_s_sleep(1);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __syncthreads();
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-          u32x4 pv[4];
-#pragma unroll
-          for (int e4 = 0; e4 < 4; ++e4)
-            pv[e4] = __builtin_amdgcn_raw_buffer_load_b128(rsS, sbase + ((mt * NT + nt) * 4 + e4) * 1024, 0, 0);
-#pragma unroll
-          for (int e4 = 0; e4 < 4; ++e4)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[mt][nt][4 * e4 + j] += __uint_as_float(pv[e4][j]);
-        }
-    }
-  }
-
   // ---- epilogue: accumulators -> LDS tile [pixel][channel] ----
   constexpr int C8 = BN / 8;
   constexpr int KIT = (BM * C8 + NTH - 1) / NTH;  // epilogue items (pixel x 8 channels) per thread
@@ -1282,10 +1205,6 @@ int launch_conv(const ConvArgs& a0, hipStream_t s) {
   if constexpr (BREG) {
     a.tiles_y = (a.H + TY - 1) / TY;
     dim3 grid = conv_grid(a, BN);
-    if (a.ks_slab != nullptr) {
-      if (OFLOW_XCD_MAP || (long long)grid.x * grid.y > a.ks_tiles) return OFLOW_E_SHAPE;
-      grid.z = 2;
-    }
     hipLaunchKernelGGL((conv_s32_kernel<KH, KW, BN, WM, WN, EPI, TY, kInS32, true>), grid, dim3(64 * WM * WN), 0, s, a);
     return launch_status();
   } else {
@@ -1343,11 +1262,9 @@ int g_bn64_8row = 0;
 // -> 144.8 / 149.9 us, step 18.96 -> 19.74 ms (profiles/r04/s26_*) -- with one workgroup per CU each halo-swap
 // barrier idles the CU's matrix cores; 128-channel 8-wave workgroups (2 x 4 of 2 row tiles, <= 128 VGPRs, four waves
 // per SIMD): z|r 141.0 / 141.1 -> 148.9 / 150.3 us, step 19.07 -> 19.65 ms (s27_*).
-// (a split-K call always takes the default tiles: the caller decides the split from its whole batch, so that pair
-// lanes of a forward compute what one lane computes, bit for bit, whatever their own sizes)
 inline bool small_grid(const ConvArgs& a, int bn) {
   return (long long)a.B * a.H * a.W < g_small_grid_px && a.stats == nullptr && a.ain == kInS32 && a.npad % 64 == 0 &&
-         bn >= 64 && a.ks_slab == nullptr;
+         bn >= 64;
 }
 
 // register-direct weights (BREG): 128-channel blocks of T > 1 convs on S32 input, given the fragment-major weights.
@@ -1449,7 +1366,7 @@ int conv_args_from_desc(const oflow_conv_s32_desc& d, ConvArgs& a) {
         (d.block_n != 64 && d.block_n != 128))
       return OFLOW_E_SHAPE;
     if (d.in_format != kInS32 || d.activation != 1 || d.out_scale != 1.0f || d.d_y0 || d.d_y1 || d.d_f32 || d.d_gru_h ||
-        d.d_gru_z || d.d_nhwc || d.d_stats || d.d_res || d.s2d || d.d_addend || d.d_ksplit_slab || d.d_ksplit_ctr)
+        d.d_gru_z || d.d_nhwc || d.d_stats || d.d_res || d.s2d || d.d_addend)
       return OFLOW_E_MODE;
     if ((d.x_pixel_stride & 127) || ((uintptr_t)d.d_fh_weights & 3) || ((uintptr_t)d.d_fh_partial & 3)) return OFLOW_E_ALIGN;
   }
@@ -1531,14 +1448,14 @@ int conv_args_from_desc(const oflow_conv_s32_desc& d, ConvArgs& a) {
     if (d.kh != 1 || d.kw != 1 || d.epilogue != 0 || d.block_n != 128 || d.in_groups != (kImgK * kImgK * 2 + 31) / 32)
       return OFLOW_E_MODE;
     if ((long long)2 * d.B * d.H * d.W >= (1ll << 31) || d.d_addend) return OFLOW_E_SHAPE;
-    return OFLOW_OK;  // (no addend, no split-K)
+    return OFLOW_OK;  // (no addend)
   }
   if (d.in_format == kInImg) {  // the stem from the image: 1x1 geometry over 5 patch groups, BN 64, epilogue 0
     if (d.kh != 1 || d.kw != 1 || d.epilogue != 0 || d.block_n != 64 || d.in_groups != (kImgK * kImgK * kImgC + 31) / 32)
       return OFLOW_E_MODE;
     if ((long long)kImgC * 4 * d.H * d.W >= (1ll << 31)) return OFLOW_E_SHAPE;
     if (d.d_addend) return OFLOW_E_MODE;
-    return OFLOW_OK;  // (no split-K)
+    return OFLOW_OK;
   }
   if (d.in_format != kInF32 && (d.x_pixel_stride & 127)) return OFLOW_E_ALIGN;  // S32 / dense fp32: whole 128-B groups
   if (d.in_format == kInF32Norm && d.x_pixel_stride != (long long)d.in_groups * 128) return OFLOW_E_SHAPE;  // dense [P][kg*32]
@@ -1563,30 +1480,6 @@ int conv_args_from_desc(const oflow_conv_s32_desc& d, ConvArgs& a) {
     if (((uintptr_t)d.d_addend & 15) || (d.addend_pixel_stride & 3) || d.addend_pixel_stride < d.N) return OFLOW_E_ALIGN;
     a.add = d.d_addend;
     a.addps = d.addend_pixel_stride;
-  }
-  if (d.d_ksplit_slab || d.d_ksplit_ctr) {
-    // split-K over the input groups: only the register-direct kernels (S32 input, fragment-major weights, multi-tap,
-    // 4-row tiles) take it; any other path this call would dispatch to runs unsplit (within the same float64 bound;
-    // the split regroups the sum over the input groups into two half-sums)
-    if (!d.d_ksplit_slab || !d.d_ksplit_ctr) return OFLOW_E_NULL;
-    if (((uintptr_t)d.d_ksplit_slab & 15) || ((uintptr_t)d.d_ksplit_ctr & 7)) return OFLOW_E_ALIGN;
-    if (d.ksplit_tiles <= 0) return OFLOW_E_SHAPE;
-    // (the register-direct instances: launch_bn / dispatch_conv -- 128-channel blocks of any multi-tap kernel but 2x2,
-    // 64- and 32-channel blocks of 3x3 ones; the GRU epilogues 1x5 / 5x1 only -- at the default tiles whatever the
-    // grid's size, see small_grid)
-    a.ks_slab = d.d_ksplit_slab;
-    const bool breg = d.in_format == kInS32 && a.wf != nullptr && use_breg(a, d.block_n, d.kh * d.kw) && d.kh * d.kw != 4 &&
-                      (d.block_n == 128 || (d.kh == 3 && d.kw == 3)) && (d.epilogue == 0 || d.kh * d.kw == 5);
-    a.ks_slab = nullptr;
-    if (breg && (d.in_groups % 2) == 0) {
-      // ksplit_tiles: the slab's capacity in (4 x 32-pixel tile, block_n channels) units of 128 * block_n floats
-      if ((long long)d.B * a.tiles_y * a.tiles_x * (d.n_pad / d.block_n) > d.ksplit_tiles) return OFLOW_E_SHAPE;
-      a.ks_slab = d.d_ksplit_slab;
-      a.ks_ctr = d.d_ksplit_ctr;
-      a.ks_tiles = d.ksplit_tiles;
-      a.kg = d.in_groups / 2;
-      a.wbytes /= 2;
-    }
   }
   return OFLOW_OK;
 }

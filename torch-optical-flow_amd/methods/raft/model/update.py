@@ -66,34 +66,20 @@ def _env_choice(var: str, default: str, choices) -> str:
 # (A/B runs only: OFLOW_CONV_BN="c2=96,mo=64" overrides entries of both)
 for _bn in (CONV_BN, CONV_BN_SIDE):
     _bn.update(parse_block_overrides("OFLOW_CONV_BN", set(CONV_BN)))
-# the flow head's output conv (3x3, 256 -> 2) above the small-grid threshold: "conv" = the 3x3 conv with 2 of its 32
-# output columns used, coords1 += in its epilogue; "col2im" = a 1x1 conv 256 -> 18 (the 9 taps' products at the input
-# pixel, 18 of 32 MFMA columns used) + a gather of the 9 taps into coords1 (oflow_flow_head_col2im_f32). In-process A/B
-# of the 8-pair step: col2im 19.99 / 19.85 ms (median / min) vs conv 19.93 / 19.74 (profiles/r04/s2_ab_fh.log): in the
-# step the other pair lane fills the CUs the 2-column conv leaves idle, so "conv" stays the default
-# r05: "tiled" = oflow_flow_head2_tiled_s32 (fp32 FMAs on an LDS-staged halo, 512 threads per 4 x 32 tile): step A/B
-# 18.81 vs 18.89 ms against "conv" (profiles/r05/s33_flow_head_tiled_ab.log; the first 256-thread form was 0.25 ms
-# slower, s32): the default until "fused"; two channel groups per staging pass: +0.6 % on the graph bench (s37), bit-identical
-# "fused" = the output conv folded into the flow head's first conv (oflow_conv_s32, OFLOW_EPI_FLOW_HEAD): conv1's
-# epilogue forms the 18 per-tap products per 64-channel slab from its fp32 tile and never writes the 256-channel
-# activation; oflow_flow_head_finish_f32 gathers them into coords1 and writes the next iteration's flow channels, so
-# flow_prep runs once per forward (11 kernels per lane iteration instead of 12). DESIGN.md §4 has the measurements.
-FLOW_HEAD_MODE = _env_choice("OFLOW_FLOW_HEAD_MODE", "fused", ("fused", "tiled", "conv", "col2im"))
+# the flow head's output conv (3x3, 256 -> 2) above the small-grid threshold (measurements: DESIGN.md §4):
+# "fused" = folded into the flow head's first conv (oflow_conv_s32, OFLOW_EPI_FLOW_HEAD): conv1's epilogue forms the 18
+#   per-tap products per 64-channel slab and never writes the 256-channel activation; oflow_flow_head_finish_f32 gathers
+#   them into coords1 and writes the next iteration's flow channels, so flow_prep runs once per forward;
+# "tiled" = oflow_flow_head2_tiled_s32, fp32 FMAs on an LDS-staged halo (the fused head's independent fp32 reference);
+# "conv"  = the 3x3 split conv with 2 of its 32 output columns used, coords1 += in its epilogue (also the fallback of
+#   the other two for a non-contiguous coords1).
+FLOW_HEAD_MODE = _env_choice("OFLOW_FLOW_HEAD_MODE", "fused", ("fused", "tiled", "conv"))
 # convf1 (7x7, 2 -> 128) straight from coords1 (_native.FlowIn, OFLOW_IN_FLOW7: each tile stages its flow window and
 # builds the patch operand in LDS) from this many pixels of the whole forward's batch up; below it flow_prep writes the
 # patch matrix and convf1 runs on the small-grid tiles. Bit-identical either way (same patch values, same k order).
 CONVF1_FROM_FLOW_MIN_PIXELS = 16384 if _env_choice("OFLOW_CONVF1_FROM_FLOW", "1", ("0", "1")) == "1" else 1 << 62  # (0: A/B)
-# r06: split-K (oflow_conv_s32, KSplit) for the update convs whose lane launch fills fewer than half of the chip's
-# two-per-CU workgroup slots: the motion conv ("mo", 3x3 256 -> 126) and both GRU candidate convs ("q", 1x5 / 5x1
-# 256 -> 128) run 224 workgroups per 4-pair lane unsplit. Each tile's two workgroups sum half of the input groups and
-# meet through an fp32 slab (csrc/conv_s32.hip). Decided from the whole forward's pixel count (as the flow head's
-# kernel), so pair lanes keep giving the single-lane flows bit for bit. Measured on the replayed 8-pair graph
-# (tools/exp/run_graph_ab.py, profiles/r06/r6s12_ab.log, one box, alternated): unsplit 17.73 ms/step, both layers split
-# 18.21, q only 17.75, motion only 18.17 -- the other lane's kernels already fill the CUs the 224-workgroup launches
-# leave idle, and the split adds a slab round trip and a second workgroup per tile. So the default is unsplit; the
-# ex5 path stays for callers whose launches run alone (tests/test_gpu_conv_ksplit.py). e.g. {"mo", "q"} to enable.
-KSPLIT_LAYERS = frozenset()
-KSPLIT_MIN_PIXELS = 16384
+# (split-K for the motion and GRU candidate convs was measured slower and removed: DESIGN.md §4 r06, §8)
+
 
 class FlowHead(nn.Module):
     def __init__(self, input_dim: int = 128, hidden_dim: int = 256) -> None:
@@ -370,10 +356,6 @@ class SplitUpdate:
         px = b * h * w if flow_head_pixels is None else int(flow_head_pixels)
         self.flow_head_fma = px < _native.FLOW_HEAD2_MAX_PIXELS
         self.f1_from_flow = px >= CONVF1_FROM_FLOW_MIN_PIXELS
-        # split-K scratch, one per runner (the calls sharing it are ordered on this runner's stream)
-        self.ks = _native.KSplit(b, h, w, dev) if KSPLIT_LAYERS and px >= KSPLIT_MIN_PIXELS else None
-        self.ks_mo = self.ks if "mo" in KSPLIT_LAYERS else None
-        self.ks_q = self.ks if "q" in KSPLIT_LAYERS else None
         S = _native.s32_empty
         self.hx = S(b, h, w, 8, dev)
         self.rhx = S(b, h, w, 8, dev)
@@ -385,7 +367,6 @@ class SplitUpdate:
         self.pm = None if self.f1_from_flow else S(b, h, w, 4, dev)  # convf1's patch matrix (small grids only)
         self.f1 = S(b, h, w, 4, dev)
         self.fh = S(b, h, w, 8, dev)
-        self.fh2y = None  # (B, 18, H, W) per-tap products of the flow head's output conv (flow_head_mode "col2im")
         self.flow_head_mode = getattr(block, "flow_head_mode", FLOW_HEAD_MODE)
         # "fused" (large grids only): the per-tap partial sums of the flow head, one buffer per runner; flow_for = the
         # coords1 storage whose flow the GRU inputs' flow channels hold (written by the finish kernel: flow_prep skipped)
@@ -433,9 +414,6 @@ class SplitUpdate:
             "mo": CW(enc.conv.weight, enc.conv.bias, 128),
             "fh1": CW(fh.conv1.weight, fh.conv1.bias, 256),
             "fh2": CW(fh.conv2.weight, fh.conv2.bias, 32),
-            # the output conv as a 1x1 conv C -> 18 (channel (ky*3+kx)*2 + c: tap (ky, kx)'s share of output c, taken at
-            # the input pixel) + oflow_flow_head_col2im_f32, which gathers the 9 taps and adds the bias into coords1
-            "fh2T": CW(fh.conv2.weight.detach().float().permute(2, 3, 0, 1).reshape(18, -1, 1, 1), None, 32),
             "fh2_bias": fh.conv2.bias.detach().float().contiguous(),
             # small grids: the 2-channel output conv as fp32 FMAs (oflow_flow_head2_s32) on the conv's own weights
             "fh2_f32": (fh.conv2.weight.detach().float().contiguous(), fh.conv2.bias.detach().float().contiguous()),
@@ -494,7 +472,6 @@ class SplitUpdate:
     def update(self, corr_in, coords1: Tensor, need_mask: bool, mask_out: Optional[Tensor] = None) -> Optional[Tensor]:
         """Everything of one update after the lookup; ``corr_in`` is convc1's input (F32In)."""
         V, conv, w = _native.S32Slice, _native.conv_s32, self.w
-        b, h, wd = self.shape
         # The motion encoder's two branches are independent (update.py:116-121): the flow branch (flow prep, convf1,
         # convf2) runs on a side stream beside the correlation branch (convc1, convc2), both MFMA-latency bound, and
         # joins before the motion conv. The side stream starts after the lookup, which thus runs alone (its bench
@@ -527,12 +504,12 @@ class SplitUpdate:
             conv(V(self.c1), w["c2"], bns["c2"], "relu", y0=V(self.cf, 0, 6))
             conv(f1_in, w["f1"], bns["f1"], "relu", y0=V(self.f1))
             conv(V(self.f1), w["f2"], bns["f2"], "relu", y0=V(self.cf, 6, 2))
-        conv(V(self.cf), w["mo"], bns["mo"], "relu", y0=V(self.hx, 4, 4), y1=V(self.rhx, 4, 4), ksplit=self.ks_mo)
+        conv(V(self.cf), w["mo"], bns["mo"], "relu", y0=V(self.hx, 4, 4), y1=V(self.rhx, 4, 4))
         for tag, gx in zip(("1", "2"), self.gx):
             conv(V(self.hx), w["zr" + tag], bns["gru"], epilogue=1, y0=V(self.rhx, 0, 4), gru_h=self.hm, gru_z=self.z,
                  addend=gx[:, :256])
             conv(V(self.rhx), w["q" + tag], bns["gru"], epilogue=2, y0=V(self.hx, 0, 4), gru_h=self.hm, gru_z=self.z,
-                 addend=gx[:, 256:], ksplit=self.ks_q)
+                 addend=gx[:, 256:])
         net = V(self.hx, 0, 4)
         if fused:
             # conv1 with the flow-head epilogue, then the gather: coords1 += conv2(relu(conv1(net))) (raft.py:133) and
@@ -546,11 +523,6 @@ class SplitUpdate:
             _native.flow_head2(V(self.fh), *w["fh2_f32"], coords1)  # coords1 += conv2(.) (raft.py:133)
         elif self.flow_head_mode == "tiled" and coords1.is_contiguous():
             _native.flow_head2_tiled(V(self.fh), *w["fh2_tiled"], coords1)  # coords1 += conv2(.) (raft.py:133)
-        elif self.flow_head_mode == "col2im" and coords1.is_contiguous():
-            if self.fh2y is None:
-                self.fh2y = torch.empty((b, 18, h, wd), device=coords1.device, dtype=torch.float32)
-            conv(V(self.fh), w["fh2T"], 32, f32=self.fh2y)
-            _native.flow_head_col2im(self.fh2y, w["fh2_bias"], coords1)  # coords1 += conv2(.) (raft.py:133)
         else:
             conv(V(self.fh), w["fh2"], 32, f32=coords1, f32_accumulate=True)
         return self._mask(net, coords1, mask_out) if need_mask else None

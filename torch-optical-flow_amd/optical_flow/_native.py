@@ -20,7 +20,7 @@ from . import _ops
 _LIB_PATH = os.environ.get(
     "OFLOW_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib", "liboflow_hip.so")
 )
-ABI_VERSION = 2
+ABI_VERSION = 3
 MAX_LEVELS = 8
 MAX_RADIUS = 7
 # grids below this many pixels run the flow head output conv as oflow_flow_head2_s32 (fp32 FMAs), larger ones as
@@ -103,7 +103,6 @@ class ConvS32Desc(ctypes.Structure):
         ("d_gru_h", _P), ("d_gru_z", _P), ("gru_channels", _I),
         ("d_nhwc", _P), ("d_stats", _P), ("d_res", _P), ("res_pixel_stride", _L),
         ("nhwc_pixel_stride", _I), ("res_activation", _I), ("s2d", _I), ("d_addend", _P), ("addend_pixel_stride", _L),
-        ("d_ksplit_slab", _P), ("d_ksplit_ctr", _P), ("ksplit_tiles", _L),
         ("d_fh_weights", _P), ("d_fh_partial", _P), ("fh_slabs", _I),
     ]
 
@@ -1081,18 +1080,6 @@ def conv_tiles(h: int, w: int) -> int:
     return ((h + 3) // 4) * ((w + 31) // 32)
 
 
-class KSplit:
-    """Split-K scratch for oflow_conv_s32 (include/oflow.h): an fp32 partial slab of ``tiles`` (4 x 32-pixel tile,
-    128-channel block) units and its [ticket, published] counters, zeroed here once. Calls sharing one KSplit must be
-    stream-ordered (one per update lane)."""
-
-    def __init__(self, b: int, h: int, w: int, device, block_n: int = 128, blocks: int = 1) -> None:
-        self.tiles = b * conv_tiles(h, w) * blocks  # (blocks: channel blocks of block_n per tile)
-        self.block_n = block_n
-        self.slab = torch.empty(self.tiles * 128 * block_n, device=device, dtype=torch.float32)
-        self.ctr = torch.zeros(2 * self.tiles, device=device, dtype=torch.int32)
-
-
 def _conv_desc(x, cw: ConvWeights, block_n: int) -> ConvS32Desc:
     """The fields every oflow_conv_s32 call sets; the rest stays zero (off) for the caller to fill by name."""
     b, h, w = x.bhw
@@ -1106,14 +1093,13 @@ def _conv_desc(x, cw: ConvWeights, block_n: int) -> ConvS32Desc:
 
 def conv_s32(x: S32Slice, cw: ConvWeights, block_n: int, act: str = "none", out_scale: float = 1.0, y0=None, y1=None,
              f32=None, f32_accumulate: bool = False, epilogue: int = 0, gru_h=None, gru_z=None, nhwc=None, stats=None,
-             res=None, res_act: str = "none", s2d: bool = False, addend=None, ksplit: "KSplit" = None) -> None:
+             res=None, res_act: str = "none", s2d: bool = False, addend=None) -> None:
     """Split-fp16 convolution (oflow_conv_s32). x: input S32Slice with cw.kg groups, or NhwcNormIn (3x3 only). y0/y1:
     S32Slice destinations (s2d: space-to-depth layout, half the spatial size). f32: (B, N', H, W) fp32 NCHW destination.
     nhwc: [P, N] fp32 destination. stats: instance-norm partials [B, conv_tiles(H, W), n_pad, 3]. res: S32Slice residual
     added after the activation, then res_act. epilogue 1/2: GRU gates / candidate with gru_h, gru_z ([P, CH] fp32);
     addend: fp32 [P, >= N] (row stride a multiple of 4, 16-B aligned) added before the gate activations (the GRU's
-    hoisted context term). ksplit: split-K scratch (KSplit) -- the register-direct kernels then run each tile as two
-    workgroups over half the input groups each (the sum regrouped into two half-sums); other kernels ignore it."""
+    hoisted context term)."""
     what = "conv_s32"
     if CHECK_RANGE:
         _range_check(x, f"{what} {cw.kh}x{cw.kw}")
@@ -1173,11 +1159,6 @@ def conv_s32(x: S32Slice, cw: ConvWeights, block_n: int, act: str = "none", out_
         taps, p_out = cw.kh * cw.kw, b * h * w  # (s2d only changes where the epilogue writes)
         n_exec = -(-cw.n_pad // d.block_n) * d.block_n
         _count(3 * 2 * p_out * n_exec * cw.kg * 32 * taps, 2 * p_out * cw.n * cw.cin * taps)
-    if ksplit is not None and d.d_wfrag is not None:
-        if ksplit.slab.device != x.device or ksplit.block_n < d.block_n:
-            raise RuntimeError(f"{what}: split-K scratch on another device or for narrower channel blocks")
-        d.d_ksplit_slab, d.d_ksplit_ctr = ksplit.slab.data_ptr(), ksplit.ctr.data_ptr()
-        d.ksplit_tiles = ksplit.tiles * (ksplit.block_n // d.block_n)
     with torch.cuda.device(x.device), _Timed(f"conv{cw.kh}x{cw.kw}", x.device):
         _check(load().oflow_conv_s32(ctypes.byref(d), _stream(x.device)), what)
 
