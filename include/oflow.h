@@ -28,6 +28,9 @@
  *                              and its autograd)
  *   oflow_forward_interpolate_f32 <- nothing in the reference: it produces the flow_init that
  *                              methods/raft/model/raft.py:122-123 consumes (upstream RAFT's forward_interpolate)
+ *   oflow_augment_stats_u8, oflow_augment_dense_f32, oflow_augment_sparse_flow_f32 <- methods/raft/data/augmentor.py:43-324
+ *                              (FlowAugmentor, SparseFlowAugmentor: PIL ColorJitter, cv2.resize, eraser, flips, crop)
+ *                              + methods/raft/data/dataset.py:114-119 (fp32 flow, the dense valid mask)
  */
 #ifndef OFLOW_H_
 #define OFLOW_H_
@@ -553,6 +556,59 @@ int oflow_sequence_loss_backward_f32(const float* d_grad_out, const float* const
  *   scratch, O((H*W)^2) candidate evaluations per image. B <= 65535, H*W <= 2^30.
  */
 int oflow_forward_interpolate_f32(const float* d_flow, int B, int H, int W, float* d_out, void* stream);
+
+/*
+ * Training-batch augmentation (csrc/augment.hip): the reference's FlowAugmentor / SparseFlowAugmentor
+ * (methods/raft/data/augmentor.py) for a batch of B samples of one source size, on the device. The random decisions are
+ * made on the host (data.augmentor.*.sample) and arrive as d_params, a (B, OFLOW_AUG_PARAM_DOUBLES) float64 array; row:
+ *    [0]      asymmetric (0 / 1)
+ *    [1..8]   frame 1: the op order (4 entries, 0 brightness, 1 contrast, 2 saturation, 3 hue: torchvision's fn_idx),
+ *             then the brightness, contrast, saturation and hue factors
+ *    [9..16]  frame 2, the same (a symmetric draw repeats frame 1's)
+ *    [17]     number of eraser rectangles (0..2);  [18..25] two rectangles (x0, y0, dx, dy) in source pixels
+ *    [26]     do_resize;  [27] scale_x;  [28] scale_y;  [29] hflip;  [30] vflip;  [31] crop y0;  [32] crop x0
+ *    [33..]   reserved, zero
+ * d_img1, d_img2: (B, H, W, 3) uint8, HWC. d_flow: (B, 2, H, W) fp32. d_stats: (B, OFLOW_AUG_STATS_WORDS) int64, ZEROED
+ * by the caller before stage 0: [0], [1] the grey sums of frame 1 / 2 in front of the contrast op, [2..4] the R, G, B
+ * sums of the jittered frame 2. Outputs: (B, 3, crop_h, crop_w), (B, 2, crop_h, crop_w), (B, crop_h, crop_w) fp32.
+ *
+ * Arithmetic (the contract; tests/augment_cases.py restates it in NumPy and the kernels equal it bit for bit):
+ *   colour jitter as Pillow computes it -- L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16; blend(d, x, f) =
+ *   (float)d + f * ((float)x - (float)d) in fp32 (one product, one sum, no FMA), truncated for 0 <= f <= 1, else clamped
+ *   to [0, 255] and truncated; brightness d = 0, saturation d = L of the pixel, contrast d = int(mean(L) + 0.5) with the
+ *   mean the exact integer sum over the image as it stands at contrast's turn, divided in float64, over BOTH frames for
+ *   a symmetric draw (the reference jitters them stacked) and per frame for an asymmetric one; hue through Pillow's
+ *   RGB -> HSV -> RGB with H += trunc(hue * 255) mod 256, also for hue 0. The eraser fills its rectangles (clipped at
+ *   the frame edge) of frame 2 with trunc(channel sum / (H*W)) of the jittered frame 2. Resize follows OpenCV's
+ *   documented INTER_LINEAR mapping: size round_half_even(n * s); f = fp32((d + 0.5) * (1 / s) - 0.5) (float64, rounded
+ *   once), i = floor(f), a = f - i, i < 0 -> (0, 0), i >= n - 1 -> (n - 1, 0); S0 * (1 - a) + S1 * a in fp32 (two
+ *   products, one sum), horizontally then vertically; image levels are then rounded half-even and clamped (OpenCV's own
+ *   8-bit path blends in fixed point: agreement with it is not measured); the flow is then multiplied by
+ *   (scale_x, scale_y) and the flips' signs in float64 and rounded once. Flips, then the crop at (y0, x0).
+ *   Dense valid = (|u| < 1000) & (|v| < 1000) of the output flow.
+ *   Sparse flow / valid under resize (resize_sparse_flow_map): source (x, y) with valid >= 1 lands at xx =
+ *   round_half_even((double)(float)x * scale_x), yy likewise, kept iff 0 < xx < wd1 and 0 < yy < ht1, value
+ *   fp32((double)flow * scale); of several sources on one pixel the LAST in row-major source order stays; unreached
+ *   pixels are 0 / 0. Without resize flow and valid pass through. The sparse class flips only horizontally.
+ * oflow_augment_stats_u8: stage 0 accumulates [0], [1]; stage 1 (after stage 0 on the same stream) accumulates [2..4]
+ *   for the samples that erase. 64-bit integer atomics: exact, the same bits on every run.
+ * oflow_augment_dense_f32: images, and with d_flow != NULL the dense flow and valid (NULL: images only, d_out_flow and
+ *   d_out_valid are not touched). Needs both stats stages. One thread per output pixel; only the crop's taps are read.
+ * oflow_augment_sparse_flow_f32: the sparse flow and valid (d_valid: (B, H, W) fp32), a gather without atomics.
+ * The kernels clamp every source index into the frame, but a crop outside the resized frame, a scale <= 0 or an op
+ * order that is no permutation gives meaningless values: callers validate the rows first (data.augmentor does).
+ * B <= 65535, H*W <= 2^28, crop_h*crop_w <= 2^28; stage 0 or 1. OFLOW_E_NULL / OFLOW_E_SHAPE before any launch.
+ */
+#define OFLOW_AUG_PARAM_DOUBLES 36
+#define OFLOW_AUG_STATS_WORDS 8
+int oflow_augment_stats_u8(const unsigned char* d_img1, const unsigned char* d_img2, const double* d_params, int B,
+                           int H, int W, int stage, long long* d_stats, void* stream);
+int oflow_augment_dense_f32(const unsigned char* d_img1, const unsigned char* d_img2, const float* d_flow,
+                            const double* d_params, const long long* d_stats, int B, int H, int W, int crop_h,
+                            int crop_w, float* d_out1, float* d_out2, float* d_out_flow, float* d_out_valid,
+                            void* stream);
+int oflow_augment_sparse_flow_f32(const float* d_flow, const float* d_valid, const double* d_params, int B, int H,
+                                  int W, int crop_h, int crop_w, float* d_out_flow, float* d_out_valid, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@
 //   convex_upsample(flow, mask) -> Tensor                                                   RAFT.upsample_flow (raft.py:73-85)
 //   convex_upsample_backward(grad_out, flow, mask, mask2) -> (grad_flow, grad_mask)         its autograd
 //   forward_interpolate(flow) -> Tensor                           warm-start flow_init (upstream RAFT's forward_interpolate)
+//   augment_batch(img1, img2, flow, valid?, params, crop_h, crop_w) -> (img1, img2, flow, valid)   data/augmentor.py:43-324
 #include <array>
 #include <torch/library.h>
 #include <ATen/ATen.h>
@@ -899,6 +900,76 @@ Tensor forward_interpolate_impl(const Tensor& flow, bool run) {
 Tensor forward_interpolate_hip(const Tensor& flow) { return forward_interpolate_impl(flow, true); }
 Tensor forward_interpolate_meta(const Tensor& flow) { return forward_interpolate_impl(flow, false); }
 
+// ---------------------------------------------------------------- training-batch augmentation (augment.hip)
+using Tensor4 = std::tuple<Tensor, Tensor, Tensor, Tensor>;
+Tensor4 augment_batch_impl(const Tensor& img1, const Tensor& img2, const Tensor& flow,
+                           const c10::optional<Tensor>& valid, const Tensor& params, int64_t ch, int64_t cw,
+                           bool run) {
+  const char* what = "augment_batch";
+  const bool sparse = valid.has_value();
+  if (run) {
+    check_on_gpu(img1, "img1", what), check_on_gpu(img2, "img2", what), check_on_gpu(flow, "flow", what);
+    check_on_gpu(params, "params", what);
+    if (sparse) check_on_gpu(*valid, "valid", what);
+  }
+  TORCH_CHECK(img1.dim() == 4 && img1.size(3) == 3 && img1.sizes() == img2.sizes(), what, ": img1 ", img1.sizes(),
+              " and img2 ", img2.sizes(), " must be equal (B, H, W, 3)");
+  TORCH_CHECK(img1.scalar_type() == at::kByte && img2.scalar_type() == at::kByte, what, ": images must be uint8");
+  const int64_t b = img1.size(0), h = img1.size(1), w = img1.size(2);
+  TORCH_CHECK(flow.dim() == 4 && flow.size(0) == b && flow.size(1) == 2 && flow.size(2) == h && flow.size(3) == w,
+              what, ": flow must be (B, 2, H, W) = (", b, ", 2, ", h, ", ", w, "), got ", flow.sizes());
+  TORCH_CHECK(flow.scalar_type() == at::kFloat, what, ": flow must be float32, got ", flow.scalar_type());
+  if (sparse)
+    TORCH_CHECK(valid->dim() == 3 && valid->size(0) == b && valid->size(1) == h && valid->size(2) == w &&
+                    valid->scalar_type() == at::kFloat,
+                what, ": valid must be float32 (B, H, W), got ", valid->scalar_type(), " ", valid->sizes());
+  TORCH_CHECK(params.dim() == 2 && params.size(0) == b && params.size(1) == OFLOW_AUG_PARAM_DOUBLES &&
+                  params.scalar_type() == at::kDouble,
+              what, ": params must be float64 (B, ", OFLOW_AUG_PARAM_DOUBLES, "), got ", params.scalar_type(), " ",
+              params.sizes());
+  TORCH_CHECK(ch >= 1 && cw >= 1 && ch * cw <= (int64_t(1) << 28), what, ": crop ", ch, " x ", cw, " out of range");
+  TORCH_CHECK(b <= 65535 && h * w <= (int64_t(1) << 28), what, ": source ", img1.sizes(),
+              " is past the kernels' grid (B <= 65535, H*W <= 2^28)");
+  for (const Tensor* t : {&img2, &flow, &params})
+    TORCH_CHECK(t->device() == img1.device(), what, ": all tensors must be on one device");
+  if (sparse) TORCH_CHECK(valid->device() == img1.device(), what, ": all tensors must be on one device");
+  auto fo = flow.options();
+  Tensor o1 = at::empty({b, 3, ch, cw}, fo), o2 = at::empty({b, 3, ch, cw}, fo);
+  Tensor of = at::empty({b, 2, ch, cw}, fo), ov = at::empty({b, ch, cw}, fo);
+  if (!run || b == 0) return Tensor4(o1, o2, of, ov);
+  TORCH_CHECK(h >= 1 && w >= 1, what, ": empty source frames");
+  Tensor i1 = img1.contiguous(), i2 = img2.contiguous(), fl = flow.contiguous(), pa = params.contiguous();
+  Tensor stats = at::zeros({b, OFLOW_AUG_STATS_WORDS}, fo.dtype(at::kLong));
+  c10::hip::HIPGuardMasqueradingAsCUDA g(i1.device());
+  void* st = cur_stream();
+  const auto* p1 = i1.data_ptr<uint8_t>();
+  const auto* p2 = i2.data_ptr<uint8_t>();
+  auto* ps = reinterpret_cast<long long*>(stats.data_ptr<int64_t>());
+  for (int stage = 0; stage < 2; ++stage)
+    check_status(oflow_augment_stats_u8(p1, p2, pa.data_ptr<double>(), (int)b, (int)h, (int)w, stage, ps, st), what);
+  check_status(oflow_augment_dense_f32(p1, p2, sparse ? nullptr : fl.data_ptr<float>(), pa.data_ptr<double>(), ps,
+                                       (int)b, (int)h, (int)w, (int)ch, (int)cw, o1.data_ptr<float>(),
+                                       o2.data_ptr<float>(), sparse ? nullptr : of.data_ptr<float>(),
+                                       sparse ? nullptr : ov.data_ptr<float>(), st),
+               what);
+  if (sparse) {
+    Tensor va = valid->contiguous();
+    check_status(oflow_augment_sparse_flow_f32(fl.data_ptr<float>(), va.data_ptr<float>(), pa.data_ptr<double>(),
+                                               (int)b, (int)h, (int)w, (int)ch, (int)cw, of.data_ptr<float>(),
+                                               ov.data_ptr<float>(), st),
+                 what);
+  }
+  return Tensor4(o1, o2, of, ov);
+}
+Tensor4 augment_batch_hip(const Tensor& a, const Tensor& b, const Tensor& f, const c10::optional<Tensor>& v,
+                          const Tensor& p, int64_t ch, int64_t cw) {
+  return augment_batch_impl(a, b, f, v, p, ch, cw, true);
+}
+Tensor4 augment_batch_meta(const Tensor& a, const Tensor& b, const Tensor& f, const c10::optional<Tensor>& v,
+                           const Tensor& p, int64_t ch, int64_t cw) {
+  return augment_batch_impl(a, b, f, v, p, ch, cw, false);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(oflow, m) {
@@ -923,6 +994,7 @@ TORCH_LIBRARY(oflow, m) {
   m.def("convex_upsample(Tensor flow, Tensor mask) -> Tensor");
   m.def("convex_upsample_backward(Tensor grad_out, Tensor flow, Tensor mask, bool[2] output_mask) -> (Tensor, Tensor)");
   m.def("forward_interpolate(Tensor flow) -> Tensor");
+  m.def("augment_batch(Tensor img1, Tensor img2, Tensor flow, Tensor? valid, Tensor params, int crop_h, int crop_w) -> (Tensor, Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
@@ -947,6 +1019,7 @@ TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
   m.impl("convex_upsample", &convex_upsample_hip);
   m.impl("convex_upsample_backward", &convex_upsample_backward_hip);
   m.impl("forward_interpolate", &forward_interpolate_hip);
+  m.impl("augment_batch", &augment_batch_hip);
 }
 
 // CPU tensors reach the same kernels, whose first check raises "no CPU fallback" (there is no CPU path)
@@ -972,6 +1045,7 @@ TORCH_LIBRARY_IMPL(oflow, CPU, m) {
   m.impl("convex_upsample", &convex_upsample_hip);
   m.impl("convex_upsample_backward", &convex_upsample_backward_hip);
   m.impl("forward_interpolate", &forward_interpolate_hip);
+  m.impl("augment_batch", &augment_batch_hip);
 }
 
 TORCH_LIBRARY_IMPL(oflow, Meta, m) {
@@ -996,4 +1070,5 @@ TORCH_LIBRARY_IMPL(oflow, Meta, m) {
   m.impl("convex_upsample", &convex_upsample_meta);
   m.impl("convex_upsample_backward", &convex_upsample_backward_meta);
   m.impl("forward_interpolate", &forward_interpolate_meta);
+  m.impl("augment_batch", &augment_batch_meta);
 }

@@ -85,6 +85,9 @@ SYMBOLS = (
     "oflow_convex_upsample_backward_f32",
     "oflow_corr_lookup_otf_backward_f32",
     "oflow_forward_interpolate_f32",
+    "oflow_augment_stats_u8",
+    "oflow_augment_dense_f32",
+    "oflow_augment_sparse_flow_f32",
 )
 
 
@@ -311,6 +314,12 @@ def load() -> ctypes.CDLL:
     lib.oflow_corr_lookup_otf_backward_f32.argtypes = [P, P, PP, IP, IP, I, P, I, I, I, I, I, P, P, P, P]
     lib.oflow_forward_interpolate_f32.restype = I
     lib.oflow_forward_interpolate_f32.argtypes = [P, I, I, I, P, P]
+    lib.oflow_augment_stats_u8.restype = I
+    lib.oflow_augment_stats_u8.argtypes = [P, P, P, I, I, I, I, P, P]
+    lib.oflow_augment_dense_f32.restype = I
+    lib.oflow_augment_dense_f32.argtypes = [P, P, P, P, P, I, I, I, I, I, P, P, P, P, P]
+    lib.oflow_augment_sparse_flow_f32.restype = I
+    lib.oflow_augment_sparse_flow_f32.argtypes = [P, P, P, I, I, I, I, I, P, P, P]
     v = lib.oflow_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liboflow_hip.so ABI version {v}, expected {ABI_VERSION}: rebuild the library")
@@ -526,6 +535,22 @@ def forward_interpolate(flow: torch.Tensor) -> torch.Tensor:
     float64, ties to the lowest source index, zeros when nothing lands. No autograd formula: the input is detached."""
     fl = _tensor(flow, "flow", "forward_interpolate")
     return _run("forward_interpolate", fl.device, ops().forward_interpolate, fl.detach())
+
+
+AUG_PARAM_DOUBLES = 36  # include/oflow.h OFLOW_AUG_PARAM_DOUBLES
+
+
+def augment_batch(img1: torch.Tensor, img2: torch.Tensor, flow: torch.Tensor, valid: Optional[torch.Tensor],
+                  params: torch.Tensor, crop_h: int, crop_w: int):
+    """FlowAugmentor / SparseFlowAugmentor on a batch (``torch.ops.oflow.augment_batch``, include/oflow.h
+    oflow_augment_*): uint8 (B, H, W, 3) frames, fp32 (B, 2, H, W) flow, for the sparse class fp32 (B, H, W) ``valid``,
+    and the packed (B, AUG_PARAM_DOUBLES) float64 parameter rows on the same device -> fp32 (img1, img2, flow, valid)
+    of the crop. The rows are taken as they are: ``data.augmentor`` validates them. No autograd formula."""
+    what = "augment_batch"
+    a = _tensor(img1, "img1", what)
+    va = None if valid is None else _tensor(valid, "valid", what).detach()
+    return _run(what, a.device, ops().augment_batch, a, _tensor(img2, "img2", what), _tensor(flow, "flow", what).detach(),
+                va, _tensor(params, "params", what), int(crop_h), int(crop_w))
 
 
 FLOW2RGB_METHODS = {"baker": 0, "hsv": 1, "meister": 2}

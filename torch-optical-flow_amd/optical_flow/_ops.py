@@ -30,7 +30,8 @@ Autograd:
 The tiled / NHWC lookups and the raw fp16 on-the-fly ops (``corr_otf_prepare`` / ``corr_lookup_otf``) are the inference
 layouts and have no autograd formula; ``flow_error_stats`` (the metrics' accumulating reduction) has none either, nor
 has ``forward_interpolate`` (the warm-start initialiser, csrc/forward_interpolate.hip: a nearest-landed-source selection
-in float64, piecewise constant in its input; callers detach the input, ``model.utils.forward_interpolate``).
+in float64, piecewise constant in its input; callers detach the input, ``model.utils.forward_interpolate``), nor has
+``augment_batch`` (the training-batch augmentation, csrc/augment.hip: integer image levels and a resampled ground truth).
 """
 from __future__ import annotations
 
@@ -63,6 +64,7 @@ OPS = (
     "corr_lookup_alt",
     "corr_lookup_alt_backward",
     "forward_interpolate",
+    "augment_batch",
 )
 _loaded = False
 
