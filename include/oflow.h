@@ -20,6 +20,8 @@
  *   oflow_stem_patches_s32, oflow_norm_*, oflow_conv_s32 <- methods/raft/model/extractor.py:35-231 (encoders)
  *   oflow_convex_upsample_f32 <- methods/raft/model/raft.py:73-85 (RAFT.upsample_flow)
  *   oflow_convex_upsample_backward_f32 <- the same lines under autograd (the training step, raft.py:149-175)
+ *   oflow_conv2d_backward_input_f32, oflow_conv2d_backward_weight_f32 <- methods/raft/model/update.py:31-161 under
+ *                              autograd (the update block's nn.Conv2d layers in the training step, raft.py:149-175)
  *   oflow_flow_stats_f32, oflow_flow2rgb_f32 <- optical_flow/visualization/flow2rgb.py:19-73 (+ visualization/methods/)
  *   oflow_flow_pack_f32     <- optical_flow/io/middlebury.py:43-71, optical_flow/io/pfm.py:79-104 (file payloads)
  *   oflow_flow_error_stats_f32 <- optical_flow/metrics/epe.py:24-65 (AverageEndPointError.update, end_point_error)
@@ -436,6 +438,33 @@ int oflow_convex_upsample_f32(const float* d_flow, const float* d_mask, int B, i
  */
 int oflow_convex_upsample_backward_f32(const float* d_grad_out, const float* d_flow, const float* d_mask, int B, int H,
                                        int W, float* d_grad_flow, float* d_grad_mask, float* d_scratch, void* stream);
+
+/*
+ * Backward of the update block's convolutions (methods/raft/model/update.py:31-161 under autograd, the training step
+ * raft.py:149-175; csrc/conv_backward.hip). Stride 1, dilation 1, groups 1, odd kh, kw <= 7 with zero padding
+ * (kh/2, kw/2), contiguous fp32 NCHW: d_grad_out (B, Cout, H, W), d_x (B, Cin, H, W), d_weight (Cout, Cin, kh, kw).
+ * With oy = ky - kh/2, ox = kx - kw/2 and out-of-image terms zero:
+ *   d_grad_input[b, c, y, x]    = sum_{ky, kx, n} grad_out[b, n, y - oy, x - ox] * weight[n, c, ky, kx]
+ *   d_grad_weight[n, c, ky, kx] = sum_{b, y, x}   grad_out[b, n, y, x] * x[b, c, y + oy, x + ox]
+ *   d_grad_bias[n]              = sum_{b, y, x}   grad_out[b, n, y, x]
+ * on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 fma chains). Every element of a requested output is
+ * written (the caller zeroes nothing), in a fixed summation order and with no atomics: two calls give the same bits.
+ * Sizes: Cout, Cin <= 65535, B*H*W <= 65535 * oflow_conv2d_backward_weight_slab_pixels(), Cout*Cin*kh*kw < 2^31; a
+ * non-positive size, an even or > 7 kernel size or a size past these limits is OFLOW_E_SHAPE.
+ *
+ * oflow_conv2d_backward_weight_f32 splits the pixel sum into slabs of oflow_conv2d_backward_weight_slab_pixels()
+ * flattened (b, y, x) pixels; each slab's partial goes to d_workspace and a second kernel adds the slabs in ascending
+ * order. d_workspace: oflow_conv2d_backward_weight_workspace_floats(...) floats (0 for a shape the call would refuse),
+ * no initialisation needed. d_grad_weight or d_grad_bias may be NULL (that gradient is not formed; both NULL is
+ * OFLOW_E_NULL); d_x may be NULL when d_grad_weight is.
+ */
+int oflow_conv2d_backward_input_f32(const float* d_grad_out, const float* d_weight, int B, int Cout, int Cin, int H, int W,
+                                    int kh, int kw, float* d_grad_input, void* stream);
+int oflow_conv2d_backward_weight_slab_pixels(void);
+long long oflow_conv2d_backward_weight_workspace_floats(int B, int Cout, int Cin, int H, int W, int kh, int kw);
+int oflow_conv2d_backward_weight_f32(const float* d_grad_out, const float* d_x, int B, int Cout, int Cin, int H, int W,
+                                     int kh, int kw, float* d_grad_weight, float* d_grad_bias, float* d_workspace,
+                                     void* stream);
 
 /*
  * Backward of the correlation (methods/raft/model/corr.py:38-87 + utils.py:64-80 under autograd, the training step

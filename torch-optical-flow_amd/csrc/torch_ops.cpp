@@ -26,6 +26,8 @@
 //   sequence_loss_backward(grad_out, flow_preds, flow_gt, valid, weights, max_flow, need) -> Tensor[]   its autograd
 //   convex_upsample(flow, mask) -> Tensor                                                   RAFT.upsample_flow (raft.py:73-85)
 //   convex_upsample_backward(grad_out, flow, mask, mask2) -> (grad_flow, grad_mask)         its autograd
+//   conv2d_same(x, weight, bias?) -> Tensor                       nn.Conv2d, stride 1, "same" zero padding (update.py:31-161)
+//   conv2d_same_backward(grad_out, x, weight, mask3) -> (grad_x, grad_weight, grad_bias)    its autograd (conv_backward.hip)
 //   forward_interpolate(flow) -> Tensor                           warm-start flow_init (upstream RAFT's forward_interpolate)
 //   augment_batch(img1, img2, flow, valid?, params, crop_h, crop_w) -> (img1, img2, flow, valid)   data/augmentor.py:43-324
 #include <array>
@@ -878,6 +880,83 @@ std::tuple<Tensor, Tensor> convex_upsample_backward_meta(const Tensor& go, const
   return convex_upsample_backward_impl(go, fl, mk, om, false);
 }
 
+// ---------------------------------------------------------------- update-block convolutions under autograd (conv_backward.hip)
+// The geometry the native backward covers: stride 1, dilation 1, groups 1, odd kernel <= 7, zero padding (kh/2, kw/2).
+void check_conv_same(const Tensor& x, const Tensor& weight, const char* what) {
+  TORCH_CHECK(x.dim() == 4 && weight.dim() == 4 && weight.size(1) == x.size(1), what, ": x ", x.sizes(),
+              " must be (B, Cin, H, W) and weight ", weight.sizes(), " (Cout, Cin, kh, kw) (groups = 1)");
+  const int64_t kh = weight.size(2), kw = weight.size(3);
+  TORCH_CHECK(kh % 2 == 1 && kw % 2 == 1 && kh <= 7 && kw <= 7, what, ": kernel ", kh, " x ", kw,
+              " is not supported (odd sizes up to 7, stride 1, zero padding (kh/2, kw/2))");
+  TORCH_CHECK(x.scalar_type() == at::kFloat && weight.scalar_type() == at::kFloat, what, ": x and weight must be float32, got ",
+              x.scalar_type(), " and ", weight.scalar_type());
+  TORCH_CHECK(x.device() == weight.device(), what, ": x and weight are on different devices");
+  TORCH_CHECK(weight.size(0) >= 1 && weight.size(1) >= 1, what, ": weight ", weight.sizes(), " has no channels");
+}
+
+Tensor conv2d_same_impl(const Tensor& x, const Tensor& weight, const c10::optional<Tensor>& bias, bool run) {
+  const char* what = "conv2d_same";
+  if (run) check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
+  check_conv_same(x, weight, what);
+  if (bias.has_value())
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == weight.size(0) && bias->scalar_type() == at::kFloat &&
+                    bias->device() == x.device(),
+                what, ": bias must be float32 (Cout) on x's device, got ", bias->scalar_type(), " ", bias->sizes());
+  if (!run) return at::empty({x.size(0), weight.size(0), x.size(2), x.size(3)}, x.options());
+  // the forward is the nn.Conv2d's own call (ATen / MIOpen): the same bits; only the backward is replaced
+  return at::conv2d(x, weight, bias, {1, 1}, {weight.size(2) / 2, weight.size(3) / 2}, {1, 1}, 1);
+}
+Tensor conv2d_same_hip(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b) { return conv2d_same_impl(x, w, b, true); }
+Tensor conv2d_same_meta(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b) { return conv2d_same_impl(x, w, b, false); }
+
+// (grad_x, grad_weight, grad_bias); an output not wanted is an empty (0-element) tensor and is not formed. The K-slab
+// workspace of the weight / bias gradient is allocated here (uninitialised: the kernels write all of it they read).
+using Tensor3 = std::tuple<Tensor, Tensor, Tensor>;
+Tensor3 conv2d_same_backward_impl(const Tensor& gout, const Tensor& x, const Tensor& weight, std::array<bool, 3> om, bool run) {
+  const char* what = "conv2d_same backward";
+  if (run) check_on_gpu(gout, "grad_out", what), check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
+  check_conv_same(x, weight, what);
+  const int64_t b = x.size(0), cin = x.size(1), h = x.size(2), w = x.size(3);
+  const int64_t cout = weight.size(0), kh = weight.size(2), kw = weight.size(3);
+  TORCH_CHECK(gout.dim() == 4 && gout.size(0) == b && gout.size(1) == cout && gout.size(2) == h && gout.size(3) == w &&
+                  gout.scalar_type() == at::kFloat,
+              what, ": grad_out ", gout.sizes(), " must be float32 (B, Cout, H, W) = (", b, ", ", cout, ", ", h, ", ", w, ")");
+  TORCH_CHECK(gout.device() == x.device(), what, ": grad_out and x are on different devices");
+  const auto opt = x.options();
+  Tensor gx = at::empty(om[0] ? x.sizes() : at::IntArrayRef{0}, opt);
+  Tensor gw = at::empty(om[1] ? weight.sizes() : at::IntArrayRef{0}, opt);
+  Tensor gb = om[2] ? at::empty({cout}, opt) : at::empty({0}, opt);
+  if (!run || !(om[0] || om[1] || om[2])) return Tensor3(gx, gw, gb);
+  if (x.numel() == 0) {  // no pixels: the parameter gradients are empty sums
+    if (om[1]) gw.zero_();
+    if (om[2]) gb.zero_();
+    return Tensor3(gx, gw, gb);
+  }
+  TORCH_CHECK(b <= INT_MAX && h <= INT_MAX && w <= INT_MAX && cout <= INT_MAX && cin <= INT_MAX, what, ": x ", x.sizes(),
+              " is past the kernels' index range");
+  Tensor go = gout.contiguous(), xc = x.contiguous(), wc = weight.contiguous();
+  c10::hip::HIPGuardMasqueradingAsCUDA g(xc.device());
+  if (om[0])
+    check_status(oflow_conv2d_backward_input_f32(go.data_ptr<float>(), wc.data_ptr<float>(), (int)b, (int)cout, (int)cin,
+                                                 (int)h, (int)w, (int)kh, (int)kw, gx.data_ptr<float>(), cur_stream()),
+                 what);
+  if (om[1] || om[2]) {
+    const long long n = oflow_conv2d_backward_weight_workspace_floats((int)b, (int)cout, (int)cin, (int)h, (int)w, (int)kh, (int)kw);
+    Tensor ws = at::empty({(int64_t)n}, opt);
+    check_status(oflow_conv2d_backward_weight_f32(go.data_ptr<float>(), xc.data_ptr<float>(), (int)b, (int)cout, (int)cin,
+                                                  (int)h, (int)w, (int)kh, (int)kw, om[1] ? gw.data_ptr<float>() : nullptr,
+                                                  om[2] ? gb.data_ptr<float>() : nullptr, ws.data_ptr<float>(), cur_stream()),
+                 what);
+  }
+  return Tensor3(gx, gw, gb);
+}
+Tensor3 conv2d_same_backward_hip(const Tensor& go, const Tensor& x, const Tensor& w, std::array<bool, 3> om) {
+  return conv2d_same_backward_impl(go, x, w, om, true);
+}
+Tensor3 conv2d_same_backward_meta(const Tensor& go, const Tensor& x, const Tensor& w, std::array<bool, 3> om) {
+  return conv2d_same_backward_impl(go, x, w, om, false);
+}
+
 // ---------------------------------------------------------------- warm start (forward_interpolate.hip)
 Tensor forward_interpolate_impl(const Tensor& flow, bool run) {
   const char* what = "forward_interpolate";
@@ -993,6 +1072,8 @@ TORCH_LIBRARY(oflow, m) {
   m.def("sequence_loss_backward(Tensor grad_out, Tensor[] flow_preds, Tensor flow_gt, Tensor valid, float[] weights, float max_flow, int[] need) -> Tensor[]");
   m.def("convex_upsample(Tensor flow, Tensor mask) -> Tensor");
   m.def("convex_upsample_backward(Tensor grad_out, Tensor flow, Tensor mask, bool[2] output_mask) -> (Tensor, Tensor)");
+  m.def("conv2d_same(Tensor x, Tensor weight, Tensor? bias) -> Tensor");
+  m.def("conv2d_same_backward(Tensor grad_out, Tensor x, Tensor weight, bool[3] output_mask) -> (Tensor, Tensor, Tensor)");
   m.def("forward_interpolate(Tensor flow) -> Tensor");
   m.def("augment_batch(Tensor img1, Tensor img2, Tensor flow, Tensor? valid, Tensor params, int crop_h, int crop_w) -> (Tensor, Tensor, Tensor, Tensor)");
 }
@@ -1018,6 +1099,8 @@ TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
   m.impl("sequence_loss_backward", &sequence_loss_backward_hip);
   m.impl("convex_upsample", &convex_upsample_hip);
   m.impl("convex_upsample_backward", &convex_upsample_backward_hip);
+  m.impl("conv2d_same", &conv2d_same_hip);
+  m.impl("conv2d_same_backward", &conv2d_same_backward_hip);
   m.impl("forward_interpolate", &forward_interpolate_hip);
   m.impl("augment_batch", &augment_batch_hip);
 }
@@ -1044,6 +1127,8 @@ TORCH_LIBRARY_IMPL(oflow, CPU, m) {
   m.impl("sequence_loss_backward", &sequence_loss_backward_hip);
   m.impl("convex_upsample", &convex_upsample_hip);
   m.impl("convex_upsample_backward", &convex_upsample_backward_hip);
+  m.impl("conv2d_same", &conv2d_same_hip);
+  m.impl("conv2d_same_backward", &conv2d_same_backward_hip);
   m.impl("forward_interpolate", &forward_interpolate_hip);
   m.impl("augment_batch", &augment_batch_hip);
 }
@@ -1069,6 +1154,8 @@ TORCH_LIBRARY_IMPL(oflow, Meta, m) {
   m.impl("sequence_loss_backward", &sequence_loss_backward_meta);
   m.impl("convex_upsample", &convex_upsample_meta);
   m.impl("convex_upsample_backward", &convex_upsample_backward_meta);
+  m.impl("conv2d_same", &conv2d_same_meta);
+  m.impl("conv2d_same_backward", &conv2d_same_backward_meta);
   m.impl("forward_interpolate", &forward_interpolate_meta);
   m.impl("augment_batch", &augment_batch_meta);
 }

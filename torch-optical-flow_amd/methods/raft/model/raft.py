@@ -118,6 +118,10 @@ class RAFT(nn.Module):
         # forward's fused kernel, backward csrc/upsample_backward.hip); "aten": the reference's composition (softmax,
         # unfold, broadcast product, sum). Without autograd the fused kernel runs either way.
         self.upsample_impl = "native"
+        # how autograd on the GPU differentiates the update block's convolutions: "aten" (default): the nn.Conv2d
+        # modules (MIOpen); "native": torch.ops.oflow.conv2d_same, the same forward with the dgrad / wgrad kernels of
+        # csrc/conv_backward.hip (fp32 MFMA, no atomics, bit-reproducible). The encoders stay on ATen either way.
+        self.conv_backward_impl = "aten"
         self.encoder_streams = True  # cnet beside fnet + the corr pyramid (inference, split encoders)
         self.fnet_streams = True  # with encoder_streams: fnet's image0 and image1 halves on two streams
         # split update loop over >= 2 pairs (CorrBlock): the pairs' two halves run on two streams so that one half's
@@ -185,7 +189,8 @@ class RAFT(nn.Module):
         forward with ``hparams.iters`` refinements, ``sequence_loss`` with ``hparams.gamma``, ``epe_train`` updated with
         the last prediction; returns the loss for the caller's ``backward()`` and optimizer. The 1 / 3 / 5 px shares
         the reference logs are kept on ``last_train_metrics``. On the GPU every step autograd differentiates outside
-        the convolutions is a native kernel: correlation, convex upsampling, sequence loss."""
+        the convolutions is a native kernel: correlation, convex upsampling, sequence loss; with
+        ``conv_backward_impl = "native"`` the update block's convolutions are too (csrc/conv_backward.hip)."""
         img0, img1, flow, valid = batch
         flow_predictions = self(img0, img1, iters=self.hparams.iters)
         loss, metrics = sequence_loss(flow_predictions, flow, valid, gamma=self.hparams.gamma)
@@ -374,6 +379,8 @@ class RAFT(nn.Module):
             self._range_pending.append(snap)
 
     def _forward(self, image0: Tensor, image1: Tensor, iters: int, flow_init: Optional[Tensor], test_mode: bool):
+        if self.conv_backward_impl not in ("aten", "native"):
+            raise ValueError(f"conv_backward_impl must be 'aten' or 'native', got {self.conv_backward_impl!r}")
         if (NATIVE_NORMALIZE and image0.is_cuda and image1.is_cuda and image0.dtype == image1.dtype == torch.float32
                 and image0.shape == image1.shape
                 and not (torch.is_grad_enabled() and (image0.requires_grad or image1.requires_grad))):
@@ -476,6 +483,7 @@ class RAFT(nn.Module):
                 return coords1 - coords0, flow_up
             return flow_predictions
 
+        self.update_block.conv_backward_impl = self.conv_backward_impl
         net, inp = torch.split(cnet_out, [hdim, cdim], dim=1)
         net = torch.tanh(net)
         inp = torch.relu(inp)

@@ -81,7 +81,38 @@ CONVF1_FROM_FLOW_MIN_PIXELS = 16384 if _env_choice("OFLOW_CONVF1_FROM_FLOW", "1"
 # (split-K for the motion and GRU candidate convs was measured slower and removed: DESIGN.md §4 r06, §8)
 
 
+CONV_BACKWARD_IMPLS = ("aten", "native")
+
+
+def native_backward_conv(conv: nn.Module, x: Tensor) -> bool:
+    """Whether ``conv(x)`` can run as ``torch.ops.oflow.conv2d_same`` (same forward, backward csrc/conv_backward.hip):
+    a stride-1, dilation-1, groups-1 ``nn.Conv2d`` with an odd kernel <= 7 and zero padding (kh // 2, kw // 2), fp32,
+    on the GPU, while autograd is recording."""
+    if not (isinstance(conv, nn.Conv2d) and x.is_cuda and torch.is_grad_enabled()):
+        return False
+    if not (x.requires_grad or conv.weight.requires_grad or (conv.bias is not None and conv.bias.requires_grad)):
+        return False
+    kh, kw = conv.kernel_size
+    return (conv.stride == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and kh % 2 == 1 and kw % 2 == 1
+            and kh <= 7 and kw <= 7 and conv.padding == (kh // 2, kw // 2) and conv.padding_mode == "zeros"
+            and x.dim() == 4 and x.dtype == torch.float32 and conv.weight.dtype == torch.float32
+            and not torch.is_autocast_enabled())
+
+
+def conv_forward(conv: nn.Module, x: Tensor, impl: str = "aten") -> Tensor:
+    """``conv(x)``; with ``impl`` "native" (``RAFT.conv_backward_impl``) and a convolution ``native_backward_conv``
+    accepts, the same forward recorded as ``torch.ops.oflow.conv2d_same``, which autograd differentiates with the
+    native dgrad / wgrad kernels. Anything else (CPU tensors, no autograd, other geometry) calls the module."""
+    if impl not in CONV_BACKWARD_IMPLS:
+        raise ValueError(f"conv_backward_impl must be 'aten' or 'native', got {impl!r}")
+    if impl == "native" and native_backward_conv(conv, x):
+        return _native.ops().conv2d_same(x, conv.weight, conv.bias)
+    return conv(x)
+
+
 class FlowHead(nn.Module):
+    conv_backward_impl = "aten"  # set by BasicUpdateBlock.forward (see conv_forward)
+
     def __init__(self, input_dim: int = 128, hidden_dim: int = 256) -> None:
         super().__init__()
         self.conv1 = nn.Conv2d(input_dim, hidden_dim, 3, padding=1)
@@ -89,11 +120,14 @@ class FlowHead(nn.Module):
         self.relu = nn.ReLU(inplace=True)
 
     def forward(self, x: Tensor) -> Tensor:
-        return self.conv2(self.relu(self.conv1(x)))
+        impl = self.conv_backward_impl
+        return conv_forward(self.conv2, self.relu(conv_forward(self.conv1, x, impl)), impl)
 
 
 class SepConvGRU(nn.Module):
     """GRU with a horizontal (1x5) then a vertical (5x1) pass (`update.py:69-107`)."""
+
+    conv_backward_impl = "aten"  # set by BasicUpdateBlock.forward (see conv_forward)
 
     def __init__(self, hidden_dim: int = 128, input_dim: int = 192 + 128) -> None:
         super().__init__()
@@ -105,12 +139,12 @@ class SepConvGRU(nn.Module):
         self.convr2 = nn.Conv2d(cin, hidden_dim, (5, 1), padding=(2, 0))
         self.convq2 = nn.Conv2d(cin, hidden_dim, (5, 1), padding=(2, 0))
 
-    @staticmethod
-    def _step(h: Tensor, x: Tensor, convz: nn.Module, convr: nn.Module, convq: nn.Module) -> Tensor:
+    def _step(self, h: Tensor, x: Tensor, convz: nn.Module, convr: nn.Module, convq: nn.Module) -> Tensor:
+        impl = self.conv_backward_impl
         hx = torch.cat([h, x], dim=1)
-        z = torch.sigmoid(convz(hx))
-        r = torch.sigmoid(convr(hx))
-        q = torch.tanh(convq(torch.cat([r * h, x], dim=1)))
+        z = torch.sigmoid(conv_forward(convz, hx, impl))
+        r = torch.sigmoid(conv_forward(convr, hx, impl))
+        q = torch.tanh(conv_forward(convq, torch.cat([r * h, x], dim=1), impl))
         return (1 - z) * h + z * q
 
     def forward(self, h: Tensor, x: Tensor) -> Tensor:
@@ -120,6 +154,8 @@ class SepConvGRU(nn.Module):
 
 class BasicMotionEncoder(nn.Module):
     """Correlation (1x1 then 3x3) and flow (7x7 then 3x3) branches fused by a 3x3 conv (`update.py:110-128`)."""
+
+    conv_backward_impl = "aten"  # set by BasicUpdateBlock.forward (see conv_forward)
 
     def __init__(self, corr_levels: int, corr_radius: int) -> None:
         super().__init__()
@@ -131,14 +167,21 @@ class BasicMotionEncoder(nn.Module):
         self.conv = nn.Conv2d(64 + 192, 128 - 2, 3, padding=1)
 
     def forward(self, flow: Tensor, corr: Tensor) -> Tensor:
-        cor = F.relu(self.convc2(F.relu(self.convc1(corr))))
-        flo = F.relu(self.convf2(F.relu(self.convf1(flow))))
-        out = F.relu(self.conv(torch.cat([cor, flo], dim=1)))
+        impl = self.conv_backward_impl
+        cor = F.relu(conv_forward(self.convc2, F.relu(conv_forward(self.convc1, corr, impl)), impl))
+        flo = F.relu(conv_forward(self.convf2, F.relu(conv_forward(self.convf1, flow, impl)), impl))
+        out = F.relu(conv_forward(self.conv, torch.cat([cor, flo], dim=1), impl))
         return torch.cat([out, flow], dim=1)
 
 
 class BasicUpdateBlock(nn.Module):
-    """Motion encoder -> SepConvGRU -> flow head, plus the convex-upsampling mask head x0.25 (`update.py:131-161`)."""
+    """Motion encoder -> SepConvGRU -> flow head, plus the convex-upsampling mask head x0.25 (`update.py:131-161`).
+
+    ``conv_backward_impl`` (a plain attribute, set from ``RAFT.conv_backward_impl``): "aten" calls every convolution as
+    the module it is; "native" records the 15 convolutions as ``torch.ops.oflow.conv2d_same`` where ``conv_forward``
+    allows it (GPU, autograd recording), so their gradients come from csrc/conv_backward.hip."""
+
+    conv_backward_impl = "aten"
 
     def __init__(self, corr_levels: int, corr_radius: int, hidden_dim: int = 128) -> None:
         super().__init__()
@@ -151,10 +194,19 @@ class BasicUpdateBlock(nn.Module):
         )
 
     def forward(self, net: Tensor, inp: Tensor, corr: Tensor, flow: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+        impl = self.conv_backward_impl
+        if impl not in CONV_BACKWARD_IMPLS:
+            raise ValueError(f"conv_backward_impl must be 'aten' or 'native', got {impl!r}")
+        for part in (self.encoder, self.gru, self.flow_head):
+            part.conv_backward_impl = impl
         motion = self.encoder(flow, corr)
         net = self.gru(net, torch.cat([inp, motion], dim=1))
         delta_flow = self.flow_head(net)
-        return net, 0.25 * self.mask(net), delta_flow
+        if impl == "native":  # the mask head's Sequential, convolution by convolution
+            mask = conv_forward(self.mask[2], self.mask[1](conv_forward(self.mask[0], net, impl)), impl)
+        else:
+            mask = self.mask(net)
+        return net, 0.25 * mask, delta_flow
 
 
 class FusedUpdate:

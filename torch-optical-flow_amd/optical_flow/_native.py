@@ -88,6 +88,10 @@ SYMBOLS = (
     "oflow_augment_stats_u8",
     "oflow_augment_dense_f32",
     "oflow_augment_sparse_flow_f32",
+    "oflow_conv2d_backward_input_f32",
+    "oflow_conv2d_backward_weight_slab_pixels",
+    "oflow_conv2d_backward_weight_workspace_floats",
+    "oflow_conv2d_backward_weight_f32",
 )
 
 
@@ -320,6 +324,14 @@ def load() -> ctypes.CDLL:
     lib.oflow_augment_dense_f32.argtypes = [P, P, P, P, P, I, I, I, I, I, P, P, P, P, P]
     lib.oflow_augment_sparse_flow_f32.restype = I
     lib.oflow_augment_sparse_flow_f32.argtypes = [P, P, P, I, I, I, I, I, P, P, P]
+    lib.oflow_conv2d_backward_input_f32.restype = I
+    lib.oflow_conv2d_backward_input_f32.argtypes = [P, P, I, I, I, I, I, I, I, P, P]
+    lib.oflow_conv2d_backward_weight_slab_pixels.restype = I
+    lib.oflow_conv2d_backward_weight_slab_pixels.argtypes = []
+    lib.oflow_conv2d_backward_weight_workspace_floats.restype = L
+    lib.oflow_conv2d_backward_weight_workspace_floats.argtypes = [I, I, I, I, I, I, I]
+    lib.oflow_conv2d_backward_weight_f32.restype = I
+    lib.oflow_conv2d_backward_weight_f32.argtypes = [P, P, I, I, I, I, I, I, I, P, P, P, P]
     v = lib.oflow_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liboflow_hip.so ABI version {v}, expected {ABI_VERSION}: rebuild the library")

@@ -27,6 +27,12 @@ Autograd:
     fp16 values with the gradients kept in fp32 (fp32 MFMA). Only f1h, f2h and coords are saved: nothing that scales with
     (HW)^2 exists in either direction. grad_fmap1 is written in a fixed order (bit-reproducible); grad_fmap2 sums
     overlapping windows with fp32 atomics (last bits vary from run to run). coords get no gradient.
+  * ``conv2d_same`` (the update block's ``nn.Conv2d`` layers with ``RAFT.conv_backward_impl = "native"``): the forward
+    is ATen's convolution with the module's own arguments (stride 1, zero padding (kh // 2, kw // 2): the same bits);
+    the backward (``conv2d_same_backward``, csrc/conv_backward.hip) forms the input gradient as a gather-form GEMM and
+    the weight / bias gradients as pixel-slab partial sums added in a fixed order, all on the fp32 matrix cores: no
+    atomics, no MIOpen find step or workspace, bit-reproducible. Only the gradients ``needs_input_grad`` asks for are
+    formed (convf1's input, the detached flow, gets none).
 The tiled / NHWC lookups and the raw fp16 on-the-fly ops (``corr_otf_prepare`` / ``corr_lookup_otf``) are the inference
 layouts and have no autograd formula; ``flow_error_stats`` (the metrics' accumulating reduction) has none either, nor
 has ``forward_interpolate`` (the warm-start initialiser, csrc/forward_interpolate.hip: a nearest-landed-source selection
@@ -65,6 +71,8 @@ OPS = (
     "corr_lookup_alt_backward",
     "forward_interpolate",
     "augment_batch",
+    "conv2d_same",
+    "conv2d_same_backward",
 )
 _loaded = False
 
@@ -191,6 +199,20 @@ def _upsample_backward(ctx, grad_out):
     return (g_flow.to(flow.dtype) if need[0] else None), (g_mask.to(mask.dtype) if need[1] else None)
 
 
+def _conv_setup(ctx, inputs, output):
+    x, weight, bias = inputs
+    ctx.save_for_backward(x, weight)
+    ctx.has_bias = bias is not None
+
+
+def _conv_backward(ctx, grad_out):
+    x, weight = ctx.saved_tensors
+    need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]), ctx.has_bias and bool(ctx.needs_input_grad[2])]
+    # (a stride-0 expanded gradient, what .sum() hands over, becomes a real tensor here)
+    g_x, g_w, g_b = torch.ops.oflow.conv2d_same_backward(grad_out.contiguous(), x, weight, need)
+    return (g_x if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None)
+
+
 def _alt_setup(ctx, inputs, output):
     _fmap1, _fmap2, f1h, f2h, coords, radius = inputs
     ctx.save_for_backward(f1h, coords, *f2h)  # O(B*C*H*W): the fp32 fmaps are not kept, no volume exists
@@ -216,3 +238,4 @@ def _register_autograd() -> None:
     reg("oflow::sequence_loss", _seqloss_backward, setup_context=_seqloss_setup)
     reg("oflow::convex_upsample", _upsample_backward, setup_context=_upsample_setup)
     reg("oflow::corr_lookup_alt", _alt_backward, setup_context=_alt_setup)
+    reg("oflow::conv2d_same", _conv_backward, setup_context=_conv_setup)
