@@ -22,6 +22,8 @@
  *   oflow_convex_upsample_backward_f32 <- the same lines under autograd (the training step, raft.py:149-175)
  *   oflow_conv2d_backward_input_f32, oflow_conv2d_backward_weight_f32 <- methods/raft/model/update.py:31-161 under
  *                              autograd (the update block's nn.Conv2d layers in the training step, raft.py:149-175)
+ *   oflow_conv2d_strided_backward_*_f32, oflow_instance_norm_backward_f32, oflow_frozen_batch_norm_backward_f32
+ *                           <- methods/raft/model/extractor.py:35-231 under autograd (the encoders in the training step)
  *   oflow_flow_stats_f32, oflow_flow2rgb_f32 <- optical_flow/visualization/flow2rgb.py:19-73 (+ visualization/methods/)
  *   oflow_flow_pack_f32     <- optical_flow/io/middlebury.py:43-71, optical_flow/io/pfm.py:79-104 (file payloads)
  *   oflow_flow_error_stats_f32 <- optical_flow/metrics/epe.py:24-65 (AverageEndPointError.update, end_point_error)
@@ -465,6 +467,57 @@ long long oflow_conv2d_backward_weight_workspace_floats(int B, int Cout, int Cin
 int oflow_conv2d_backward_weight_f32(const float* d_grad_out, const float* d_x, int B, int Cout, int Cin, int H, int W,
                                      int kh, int kw, float* d_grad_weight, float* d_grad_bias, float* d_workspace,
                                      void* stream);
+
+/*
+ * The same gradients for stride 1 or 2 (the same in y and x): the encoders' convolutions
+ * (methods/raft/model/extractor.py:35-231 under autograd; csrc/conv_backward.hip). H, W are the input's; d_grad_out is
+ * (B, Cout, H', W') with H' = (H + stride - 1) / stride, W' likewise (odd sizes are legal). With py = kh/2, px = kw/2:
+ *   d_grad_input[b, c, y, x]    = sum grad_out[b, n, Y, X] * weight[n, c, ky, kx]
+ *                                 over (ky, kx, n) with stride*Y = y + py - ky, stride*X = x + px - kx inside the output
+ *   d_grad_weight[n, c, ky, kx] = sum_{b, Y, X} grad_out[b, n, Y, X] * x[b, c, stride*Y + ky - py, stride*X + kx - px]
+ *   d_grad_bias[n]              = sum_{b, Y, X} grad_out[b, n, Y, X]
+ * Every element of d_grad_input is written (at stride 2 under a 1x1 kernel three of four are exact zeros). The slabs of
+ * the weight gradient are oflow_conv2d_backward_weight_slab_pixels() flattened OUTPUT pixels. The NULL conventions, the
+ * workspace rule and the size limits are those of the stride-1 calls, with B*H'*W' in the pixel limit and B*H*W < 2^31;
+ * a stride other than 1 or 2 is OFLOW_E_SHAPE. With stride 1 the results are bit-identical to the stride-1 calls',
+ * except the weight gradient with Cin <= 4: there the (channel, tap) pairs are folded into one tile dimension (the
+ * 3 -> 64 7x7 stem: 3 tiles of 64 columns instead of 49 tap slices with 3 columns filled).
+ * oflow_conv2d_strided_backward_weight_generic_f32 is that call without the folding (what the folded path is measured
+ * and tested against).
+ */
+int oflow_conv2d_strided_backward_input_f32(const float* d_grad_out, const float* d_weight, int B, int Cout, int Cin, int H,
+                                            int W, int kh, int kw, int stride, float* d_grad_input, void* stream);
+long long oflow_conv2d_strided_backward_weight_workspace_floats(int B, int Cout, int Cin, int H, int W, int kh, int kw,
+                                                                int stride);
+int oflow_conv2d_strided_backward_weight_f32(const float* d_grad_out, const float* d_x, int B, int Cout, int Cin, int H,
+                                             int W, int kh, int kw, int stride, float* d_grad_weight, float* d_grad_bias,
+                                             float* d_workspace, void* stream);
+int oflow_conv2d_strided_backward_weight_generic_f32(const float* d_grad_out, const float* d_x, int B, int Cout, int Cin,
+                                                     int H, int W, int kh, int kw, int stride, float* d_grad_weight,
+                                                     float* d_grad_bias, float* d_workspace, void* stream);
+
+/*
+ * Backward of the encoders' norm layers with the ReLU that follows them folded in (extractor.py:35-231 under autograd;
+ * csrc/norm_backward.hip). Contiguous fp32 planes of HW elements; relu != 0: the layer's output went through a ReLU,
+ * whose mask is recomputed from x (nothing but x is kept from the forward). Per plane mu, r = 1/sqrt(var_biased + eps),
+ * xh = (x - mu) * r, g = grad_out * [output > 0] (relu) or grad_out.
+ *   oflow_instance_norm_backward_f32 (InstanceNorm2d without affine parameters; planes = B * C):
+ *     d_grad_input = r * (g - mean(g) - xh * mean(g * xh)), the statistics recomputed in fp64.
+ *   oflow_frozen_batch_norm_backward_f32 (BatchNorm2d on its running statistics: eval mode / RAFT.freeze_bn()):
+ *     y = (x - running_mean) * weight / sqrt(running_var + eps) + bias;  d_grad_input = g * weight / sqrt(running_var + eps),
+ *     d_grad_weight[c] = sum_{b, pixels} g * (x - running_mean) / sqrt(running_var + eps), d_grad_bias[c] = sum g.
+ *     A NULL output is not formed (all three NULL: OFLOW_E_NULL). d_workspace:
+ *     oflow_frozen_batch_norm_backward_workspace_floats(B, C, HW) floats, needed (and fully written) when a parameter
+ *     gradient is asked for; it holds one partial per plane, added over b in ascending order by a second kernel.
+ * No atomics, a fixed summation order: two calls give the same bits. Non-positive sizes or eps < 0: OFLOW_E_SHAPE.
+ */
+int oflow_instance_norm_backward_f32(const float* d_grad_out, const float* d_x, int planes, int HW, double eps, int relu,
+                                     float* d_grad_input, void* stream);
+long long oflow_frozen_batch_norm_backward_workspace_floats(int B, int C, int HW);
+int oflow_frozen_batch_norm_backward_f32(const float* d_grad_out, const float* d_x, const float* d_weight, const float* d_bias,
+                                         const float* d_running_mean, const float* d_running_var, int B, int C, int HW,
+                                         double eps, int relu, float* d_grad_input, float* d_grad_weight, float* d_grad_bias,
+                                         float* d_workspace, void* stream);
 
 /*
  * Backward of the correlation (methods/raft/model/corr.py:38-87 + utils.py:64-80 under autograd, the training step

@@ -28,6 +28,9 @@
 //   convex_upsample_backward(grad_out, flow, mask, mask2) -> (grad_flow, grad_mask)         its autograd
 //   conv2d_same(x, weight, bias?) -> Tensor                       nn.Conv2d, stride 1, "same" zero padding (update.py:31-161)
 //   conv2d_same_backward(grad_out, x, weight, mask3) -> (grad_x, grad_weight, grad_bias)    its autograd (conv_backward.hip)
+//   conv2d_strided(x, weight, bias?, stride) / conv2d_strided_backward(..., stride, mask3)   the encoders' nn.Conv2d, stride 1 / 2
+//   instance_norm_act(x, eps, relu) / instance_norm_act_backward(grad_out, x, eps, relu)      InstanceNorm2d [+ ReLU] (norm_backward.hip)
+//   frozen_batch_norm_act(x, weight, bias, running_mean, running_var, eps, relu) / _backward(..., mask3)   eval BatchNorm2d [+ ReLU]
 //   forward_interpolate(flow) -> Tensor                           warm-start flow_init (upstream RAFT's forward_interpolate)
 //   augment_batch(img1, img2, flow, valid?, params, crop_h, crop_w) -> (img1, img2, flow, valid)   data/augmentor.py:43-324
 #include <array>
@@ -957,6 +960,209 @@ Tensor3 conv2d_same_backward_meta(const Tensor& go, const Tensor& x, const Tenso
   return conv2d_same_backward_impl(go, x, w, om, false);
 }
 
+// ---------------------------------------------------------------- encoder convolutions under autograd (conv_backward.hip)
+// conv2d_same's geometry with stride 1 or 2: the output is ((H + s - 1) / s, (W + s - 1) / s).
+void check_conv_strided(const Tensor& x, const Tensor& weight, int64_t stride, const char* what) {
+  check_conv_same(x, weight, what);
+  TORCH_CHECK(stride == 1 || stride == 2, what, ": stride ", stride, " is not supported (1 or 2, the same in y and x)");
+}
+
+Tensor conv2d_strided_impl(const Tensor& x, const Tensor& weight, const c10::optional<Tensor>& bias, int64_t stride, bool run) {
+  const char* what = "conv2d_strided";
+  if (run) check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
+  check_conv_strided(x, weight, stride, what);
+  if (bias.has_value())
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == weight.size(0) && bias->scalar_type() == at::kFloat &&
+                    bias->device() == x.device(),
+                what, ": bias must be float32 (Cout) on x's device, got ", bias->scalar_type(), " ", bias->sizes());
+  if (!run)
+    return at::empty({x.size(0), weight.size(0), (x.size(2) + stride - 1) / stride, (x.size(3) + stride - 1) / stride},
+                     x.options());
+  // the forward is the nn.Conv2d's own call (ATen / MIOpen): the same bits; only the backward is replaced
+  return at::conv2d(x, weight, bias, {stride, stride}, {weight.size(2) / 2, weight.size(3) / 2}, {1, 1}, 1);
+}
+Tensor conv2d_strided_hip(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t s) {
+  return conv2d_strided_impl(x, w, b, s, true);
+}
+Tensor conv2d_strided_meta(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t s) {
+  return conv2d_strided_impl(x, w, b, s, false);
+}
+
+Tensor3 conv2d_strided_backward_impl(const Tensor& gout, const Tensor& x, const Tensor& weight, int64_t stride,
+                                     std::array<bool, 3> om, bool run) {
+  const char* what = "conv2d_strided backward";
+  if (run) check_on_gpu(gout, "grad_out", what), check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
+  check_conv_strided(x, weight, stride, what);
+  const int64_t b = x.size(0), cin = x.size(1), h = x.size(2), w = x.size(3);
+  const int64_t cout = weight.size(0), kh = weight.size(2), kw = weight.size(3);
+  const int64_t ho = (h + stride - 1) / stride, wo = (w + stride - 1) / stride;
+  TORCH_CHECK(gout.dim() == 4 && gout.size(0) == b && gout.size(1) == cout && gout.size(2) == ho && gout.size(3) == wo &&
+                  gout.scalar_type() == at::kFloat,
+              what, ": grad_out ", gout.sizes(), " must be float32 (B, Cout, H', W') = (", b, ", ", cout, ", ", ho, ", ", wo, ")");
+  TORCH_CHECK(gout.device() == x.device(), what, ": grad_out and x are on different devices");
+  const auto opt = x.options();
+  Tensor gx = at::empty(om[0] ? x.sizes() : at::IntArrayRef{0}, opt);
+  Tensor gw = at::empty(om[1] ? weight.sizes() : at::IntArrayRef{0}, opt);
+  Tensor gb = om[2] ? at::empty({cout}, opt) : at::empty({0}, opt);
+  if (!run || !(om[0] || om[1] || om[2])) return Tensor3(gx, gw, gb);
+  if (x.numel() == 0) {  // no pixels: the parameter gradients are empty sums
+    if (om[1]) gw.zero_();
+    if (om[2]) gb.zero_();
+    return Tensor3(gx, gw, gb);
+  }
+  TORCH_CHECK(b <= INT_MAX && h <= INT_MAX && w <= INT_MAX && cout <= INT_MAX && cin <= INT_MAX, what, ": x ", x.sizes(),
+              " is past the kernels' index range");
+  Tensor go = gout.contiguous(), xc = x.contiguous(), wc = weight.contiguous();
+  c10::hip::HIPGuardMasqueradingAsCUDA g(xc.device());
+  if (om[0])
+    check_status(oflow_conv2d_strided_backward_input_f32(go.data_ptr<float>(), wc.data_ptr<float>(), (int)b, (int)cout,
+                                                         (int)cin, (int)h, (int)w, (int)kh, (int)kw, (int)stride,
+                                                         gx.data_ptr<float>(), cur_stream()),
+                 what);
+  if (om[1] || om[2]) {
+    const long long n = oflow_conv2d_strided_backward_weight_workspace_floats((int)b, (int)cout, (int)cin, (int)h, (int)w,
+                                                                              (int)kh, (int)kw, (int)stride);
+    Tensor ws = at::empty({(int64_t)n}, opt);
+    check_status(oflow_conv2d_strided_backward_weight_f32(go.data_ptr<float>(), xc.data_ptr<float>(), (int)b, (int)cout,
+                                                          (int)cin, (int)h, (int)w, (int)kh, (int)kw, (int)stride,
+                                                          om[1] ? gw.data_ptr<float>() : nullptr,
+                                                          om[2] ? gb.data_ptr<float>() : nullptr, ws.data_ptr<float>(),
+                                                          cur_stream()),
+                 what);
+  }
+  return Tensor3(gx, gw, gb);
+}
+Tensor3 conv2d_strided_backward_hip(const Tensor& go, const Tensor& x, const Tensor& w, int64_t s, std::array<bool, 3> om) {
+  return conv2d_strided_backward_impl(go, x, w, s, om, true);
+}
+Tensor3 conv2d_strided_backward_meta(const Tensor& go, const Tensor& x, const Tensor& w, int64_t s, std::array<bool, 3> om) {
+  return conv2d_strided_backward_impl(go, x, w, s, om, false);
+}
+
+// ---------------------------------------------------------------- encoder norm layers under autograd (norm_backward.hip)
+void check_norm_input(const Tensor& x, const char* what) {
+  TORCH_CHECK(x.dim() == 4 && x.scalar_type() == at::kFloat, what, ": x must be float32 (B, C, H, W), got ", x.scalar_type(),
+              " ", x.sizes());
+  TORCH_CHECK(x.size(1) >= 1, what, ": x ", x.sizes(), " has no channels");
+}
+void check_norm_grad(const Tensor& gout, const Tensor& x, const char* what) {
+  TORCH_CHECK(gout.sizes() == x.sizes() && gout.scalar_type() == at::kFloat, what, ": grad_out ", gout.sizes(),
+              " must be float32 of x's shape ", x.sizes());
+  TORCH_CHECK(gout.device() == x.device(), what, ": grad_out and x are on different devices");
+  TORCH_CHECK(x.size(0) * x.size(1) <= INT_MAX && x.size(2) * x.size(3) <= INT_MAX, what, ": x ", x.sizes(),
+              " is past the kernels' index range");
+}
+
+// relu(instance_norm(x)) / instance_norm(x) of an nn.InstanceNorm2d without affine parameters or running statistics
+Tensor instance_norm_act_impl(const Tensor& x, double eps, bool relu, bool run) {
+  const char* what = "instance_norm_act";
+  if (run) check_on_gpu(x, "x", what);
+  check_norm_input(x, what);
+  if (!run) return at::empty(x.sizes(), x.options());
+  // the module's own ATen call (F.instance_norm with use_input_stats) and nn.ReLU's: the same bits
+  Tensor y = at::instance_norm(x, {}, {}, {}, {}, true, 0.1, eps, at::globalContext().userEnabledCuDNN());
+  return relu ? at::relu_(y) : y;
+}
+Tensor instance_norm_act_hip(const Tensor& x, double eps, bool relu) { return instance_norm_act_impl(x, eps, relu, true); }
+Tensor instance_norm_act_meta(const Tensor& x, double eps, bool relu) { return instance_norm_act_impl(x, eps, relu, false); }
+
+Tensor instance_norm_act_backward_impl(const Tensor& gout, const Tensor& x, double eps, bool relu, bool run) {
+  const char* what = "instance_norm_act backward";
+  if (run) check_on_gpu(gout, "grad_out", what), check_on_gpu(x, "x", what);
+  check_norm_input(x, what);
+  check_norm_grad(gout, x, what);
+  Tensor gx = at::empty(x.sizes(), x.options());
+  if (!run || x.numel() == 0) return gx;
+  Tensor go = gout.contiguous(), xc = x.contiguous();
+  c10::hip::HIPGuardMasqueradingAsCUDA g(xc.device());
+  check_status(oflow_instance_norm_backward_f32(go.data_ptr<float>(), xc.data_ptr<float>(), (int)(x.size(0) * x.size(1)),
+                                                (int)(x.size(2) * x.size(3)), eps, relu ? 1 : 0, gx.data_ptr<float>(),
+                                                cur_stream()),
+               what);
+  return gx;
+}
+Tensor instance_norm_act_backward_hip(const Tensor& go, const Tensor& x, double eps, bool relu) {
+  return instance_norm_act_backward_impl(go, x, eps, relu, true);
+}
+Tensor instance_norm_act_backward_meta(const Tensor& go, const Tensor& x, double eps, bool relu) {
+  return instance_norm_act_backward_impl(go, x, eps, relu, false);
+}
+
+void check_bn_params(const Tensor& x, const Tensor& weight, const Tensor& bias, const Tensor& rm, const Tensor& rv,
+                     const char* what) {
+  const char* names[4] = {"weight", "bias", "running_mean", "running_var"};
+  const Tensor* ts[4] = {&weight, &bias, &rm, &rv};
+  for (int i = 0; i < 4; ++i)
+    TORCH_CHECK(ts[i]->dim() == 1 && ts[i]->size(0) == x.size(1) && ts[i]->scalar_type() == at::kFloat &&
+                    ts[i]->device() == x.device(),
+                what, ": ", names[i], " must be float32 (C) on x's device, got ", ts[i]->scalar_type(), " ", ts[i]->sizes());
+}
+
+// relu(batch_norm(x)) / batch_norm(x) of an nn.BatchNorm2d on its running statistics (eval mode)
+Tensor frozen_batch_norm_act_impl(const Tensor& x, const Tensor& weight, const Tensor& bias, const Tensor& rm,
+                                  const Tensor& rv, double eps, bool relu, bool run) {
+  const char* what = "frozen_batch_norm_act";
+  if (run) check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
+  check_norm_input(x, what);
+  check_bn_params(x, weight, bias, rm, rv, what);
+  if (!run) return at::empty(x.sizes(), x.options());
+  // the module's own ATen call (F.batch_norm, training = False) and nn.ReLU's: the same bits
+  Tensor y = at::batch_norm(x, weight, bias, rm, rv, false, 0.1, eps, at::globalContext().userEnabledCuDNN());
+  return relu ? at::relu_(y) : y;
+}
+Tensor frozen_batch_norm_act_hip(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& rm, const Tensor& rv,
+                                 double eps, bool relu) {
+  return frozen_batch_norm_act_impl(x, w, b, rm, rv, eps, relu, true);
+}
+Tensor frozen_batch_norm_act_meta(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& rm, const Tensor& rv,
+                                  double eps, bool relu) {
+  return frozen_batch_norm_act_impl(x, w, b, rm, rv, eps, relu, false);
+}
+
+// (grad_x, grad_weight, grad_bias); an output not wanted is an empty (0-element) tensor and is not formed
+Tensor3 frozen_batch_norm_act_backward_impl(const Tensor& gout, const Tensor& x, const Tensor& weight, const Tensor& bias,
+                                            const Tensor& rm, const Tensor& rv, double eps, bool relu,
+                                            std::array<bool, 3> om, bool run) {
+  const char* what = "frozen_batch_norm_act backward";
+  if (run) check_on_gpu(gout, "grad_out", what), check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
+  check_norm_input(x, what);
+  check_bn_params(x, weight, bias, rm, rv, what);
+  check_norm_grad(gout, x, what);
+  const int64_t b = x.size(0), c = x.size(1), hw = x.size(2) * x.size(3);
+  const auto opt = x.options();
+  Tensor gx = at::empty(om[0] ? x.sizes() : at::IntArrayRef{0}, opt);
+  Tensor gw = om[1] ? at::empty({c}, opt) : at::empty({0}, opt);
+  Tensor gb = om[2] ? at::empty({c}, opt) : at::empty({0}, opt);
+  if (!run || !(om[0] || om[1] || om[2])) return Tensor3(gx, gw, gb);
+  if (x.numel() == 0) {  // no pixels: the parameter gradients are empty sums
+    if (om[1]) gw.zero_();
+    if (om[2]) gb.zero_();
+    return Tensor3(gx, gw, gb);
+  }
+  Tensor go = gout.contiguous(), xc = x.contiguous();
+  Tensor wc = weight.contiguous(), bc = bias.contiguous(), rmc = rm.contiguous(), rvc = rv.contiguous();
+  c10::hip::HIPGuardMasqueradingAsCUDA g(xc.device());
+  Tensor ws;
+  if (om[1] || om[2]) ws = at::empty({(int64_t)oflow_frozen_batch_norm_backward_workspace_floats((int)b, (int)c, (int)hw)}, opt);
+  check_status(oflow_frozen_batch_norm_backward_f32(
+                   go.data_ptr<float>(), xc.data_ptr<float>(), wc.data_ptr<float>(), bc.data_ptr<float>(),
+                   rmc.data_ptr<float>(), rvc.data_ptr<float>(), (int)b, (int)c, (int)hw, eps, relu ? 1 : 0,
+                   om[0] ? gx.data_ptr<float>() : nullptr, om[1] ? gw.data_ptr<float>() : nullptr,
+                   om[2] ? gb.data_ptr<float>() : nullptr, ws.defined() ? ws.data_ptr<float>() : nullptr, cur_stream()),
+               what);
+  return Tensor3(gx, gw, gb);
+}
+Tensor3 frozen_batch_norm_act_backward_hip(const Tensor& go, const Tensor& x, const Tensor& w, const Tensor& b,
+                                           const Tensor& rm, const Tensor& rv, double eps, bool relu,
+                                           std::array<bool, 3> om) {
+  return frozen_batch_norm_act_backward_impl(go, x, w, b, rm, rv, eps, relu, om, true);
+}
+Tensor3 frozen_batch_norm_act_backward_meta(const Tensor& go, const Tensor& x, const Tensor& w, const Tensor& b,
+                                            const Tensor& rm, const Tensor& rv, double eps, bool relu,
+                                            std::array<bool, 3> om) {
+  return frozen_batch_norm_act_backward_impl(go, x, w, b, rm, rv, eps, relu, om, false);
+}
+
 // ---------------------------------------------------------------- warm start (forward_interpolate.hip)
 Tensor forward_interpolate_impl(const Tensor& flow, bool run) {
   const char* what = "forward_interpolate";
@@ -1074,6 +1280,12 @@ TORCH_LIBRARY(oflow, m) {
   m.def("convex_upsample_backward(Tensor grad_out, Tensor flow, Tensor mask, bool[2] output_mask) -> (Tensor, Tensor)");
   m.def("conv2d_same(Tensor x, Tensor weight, Tensor? bias) -> Tensor");
   m.def("conv2d_same_backward(Tensor grad_out, Tensor x, Tensor weight, bool[3] output_mask) -> (Tensor, Tensor, Tensor)");
+  m.def("conv2d_strided(Tensor x, Tensor weight, Tensor? bias, int stride) -> Tensor");
+  m.def("conv2d_strided_backward(Tensor grad_out, Tensor x, Tensor weight, int stride, bool[3] output_mask) -> (Tensor, Tensor, Tensor)");
+  m.def("instance_norm_act(Tensor x, float eps, bool relu) -> Tensor");
+  m.def("instance_norm_act_backward(Tensor grad_out, Tensor x, float eps, bool relu) -> Tensor");
+  m.def("frozen_batch_norm_act(Tensor x, Tensor weight, Tensor bias, Tensor running_mean, Tensor running_var, float eps, bool relu) -> Tensor");
+  m.def("frozen_batch_norm_act_backward(Tensor grad_out, Tensor x, Tensor weight, Tensor bias, Tensor running_mean, Tensor running_var, float eps, bool relu, bool[3] output_mask) -> (Tensor, Tensor, Tensor)");
   m.def("forward_interpolate(Tensor flow) -> Tensor");
   m.def("augment_batch(Tensor img1, Tensor img2, Tensor flow, Tensor? valid, Tensor params, int crop_h, int crop_w) -> (Tensor, Tensor, Tensor, Tensor)");
 }
@@ -1101,6 +1313,12 @@ TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
   m.impl("convex_upsample_backward", &convex_upsample_backward_hip);
   m.impl("conv2d_same", &conv2d_same_hip);
   m.impl("conv2d_same_backward", &conv2d_same_backward_hip);
+  m.impl("conv2d_strided", &conv2d_strided_hip);
+  m.impl("conv2d_strided_backward", &conv2d_strided_backward_hip);
+  m.impl("instance_norm_act", &instance_norm_act_hip);
+  m.impl("instance_norm_act_backward", &instance_norm_act_backward_hip);
+  m.impl("frozen_batch_norm_act", &frozen_batch_norm_act_hip);
+  m.impl("frozen_batch_norm_act_backward", &frozen_batch_norm_act_backward_hip);
   m.impl("forward_interpolate", &forward_interpolate_hip);
   m.impl("augment_batch", &augment_batch_hip);
 }
@@ -1129,6 +1347,12 @@ TORCH_LIBRARY_IMPL(oflow, CPU, m) {
   m.impl("convex_upsample_backward", &convex_upsample_backward_hip);
   m.impl("conv2d_same", &conv2d_same_hip);
   m.impl("conv2d_same_backward", &conv2d_same_backward_hip);
+  m.impl("conv2d_strided", &conv2d_strided_hip);
+  m.impl("conv2d_strided_backward", &conv2d_strided_backward_hip);
+  m.impl("instance_norm_act", &instance_norm_act_hip);
+  m.impl("instance_norm_act_backward", &instance_norm_act_backward_hip);
+  m.impl("frozen_batch_norm_act", &frozen_batch_norm_act_hip);
+  m.impl("frozen_batch_norm_act_backward", &frozen_batch_norm_act_backward_hip);
   m.impl("forward_interpolate", &forward_interpolate_hip);
   m.impl("augment_batch", &augment_batch_hip);
 }
@@ -1156,6 +1380,12 @@ TORCH_LIBRARY_IMPL(oflow, Meta, m) {
   m.impl("convex_upsample_backward", &convex_upsample_backward_meta);
   m.impl("conv2d_same", &conv2d_same_meta);
   m.impl("conv2d_same_backward", &conv2d_same_backward_meta);
+  m.impl("conv2d_strided", &conv2d_strided_meta);
+  m.impl("conv2d_strided_backward", &conv2d_strided_backward_meta);
+  m.impl("instance_norm_act", &instance_norm_act_meta);
+  m.impl("instance_norm_act_backward", &instance_norm_act_backward_meta);
+  m.impl("frozen_batch_norm_act", &frozen_batch_norm_act_meta);
+  m.impl("frozen_batch_norm_act_backward", &frozen_batch_norm_act_backward_meta);
   m.impl("forward_interpolate", &forward_interpolate_meta);
   m.impl("augment_batch", &augment_batch_meta);
 }

@@ -6,6 +6,16 @@ reference's, so reference ``state_dict``s load unchanged). For GPU inference RAF
 per-tile partials merged in fp64, batch norm (eval) folded into the convolutions, ReLU / residual adds fused, and the
 stride-2 stages fed in space-to-depth layout. ``SmallEncoder``/``BottleneckBlock`` (never instantiated by RAFT,
 `raft.py:40-47`) are not provided.
+
+Under autograd on the GPU the modules' ``encoder_backward_impl`` (a plain attribute, set from
+``RAFT.encoder_backward_impl``) chooses who differentiates them: "aten" (default) calls every layer as the module it is;
+"native" records each convolution as ``torch.ops.oflow.conv2d_strided`` and each eligible norm layer, with the ReLU the
+block applies directly after it, as ``instance_norm_act`` / ``frozen_batch_norm_act`` (the same forward bit for bit;
+backward csrc/conv_backward.hip and csrc/norm_backward.hip: no atomics, no MIOpen find step, bit-reproducible).
+Eligible norms: ``InstanceNorm2d`` without affine parameters (fnet) and ``BatchNorm2d`` on its running statistics (cnet
+in eval mode / after ``RAFT.freeze_bn()``). Batch norm on batch statistics (cnet in train mode: the Chairs stage) is
+not covered: those 15 layers keep calling the module while cnet's convolutions still go native. ``GroupNorm`` and
+``norm_fn = "none"`` stay the module. CPU tensors, no-grad, autocast and the split inference path are unaffected.
 """
 from __future__ import annotations
 
@@ -34,8 +44,53 @@ def _norm_layer(norm_fn: str, planes: int, groups: int) -> nn.Module:
     raise ValueError(f"unknown norm_fn {norm_fn!r}")
 
 
+ENCODER_BACKWARD_IMPLS = ("aten", "native")
+
+
+def _native_autograd(x: Tensor) -> bool:
+    """The state the native backward ops cover: a 4-d fp32 GPU tensor, autograd recording, no autocast."""
+    return (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and torch.is_grad_enabled()
+            and not torch.is_autocast_enabled())
+
+
+def enc_conv(conv: nn.Module, x: Tensor, impl: str = "aten") -> Tensor:
+    """``conv(x)``; with ``impl`` "native" and a convolution the native backward covers (stride 1 or 2, dilation 1,
+    groups 1, odd kernel <= 7, zero padding (kh // 2, kw // 2), fp32 on the GPU while autograd records something), the
+    same forward recorded as ``torch.ops.oflow.conv2d_strided``. Anything else calls the module."""
+    if impl not in ENCODER_BACKWARD_IMPLS:
+        raise ValueError(f"encoder_backward_impl must be 'aten' or 'native', got {impl!r}")
+    if impl == "native" and isinstance(conv, nn.Conv2d) and _native_autograd(x):
+        kh, kw = conv.kernel_size
+        needs = x.requires_grad or conv.weight.requires_grad or (conv.bias is not None and conv.bias.requires_grad)
+        if (needs and conv.stride in ((1, 1), (2, 2)) and conv.dilation == (1, 1) and conv.groups == 1
+                and kh % 2 == 1 and kw % 2 == 1 and kh <= 7 and kw <= 7 and conv.padding == (kh // 2, kw // 2)
+                and conv.padding_mode == "zeros" and conv.weight.dtype == torch.float32):
+            return _native.ops().conv2d_strided(x, conv.weight, conv.bias, conv.stride[0])
+    return conv(x)
+
+
+def enc_norm_act(norm: nn.Module, x: Tensor, relu: bool, impl: str = "aten") -> Tensor:
+    """``norm(x)``, through a ReLU when ``relu``; with ``impl`` "native" and an eligible layer (see the module
+    docstring) recorded as one fused op whose backward is native. Anything else calls the module (and ``torch.relu``)."""
+    if impl not in ENCODER_BACKWARD_IMPLS:
+        raise ValueError(f"encoder_backward_impl must be 'aten' or 'native', got {impl!r}")
+    if impl == "native" and _native_autograd(x):
+        if (isinstance(norm, nn.InstanceNorm2d) and not norm.affine and not norm.track_running_stats
+                and x.requires_grad):
+            return _native.ops().instance_norm_act(x, norm.eps, relu)
+        if (isinstance(norm, nn.BatchNorm2d) and not norm.training and norm.affine and norm.running_mean is not None
+                and norm.running_var is not None and norm.weight.dtype == torch.float32
+                and (x.requires_grad or norm.weight.requires_grad or norm.bias.requires_grad)):
+            return _native.ops().frozen_batch_norm_act(x, norm.weight, norm.bias, norm.running_mean, norm.running_var,
+                                                       norm.eps, relu)
+    y = norm(x)
+    return torch.relu(y) if relu else y
+
+
 class ResidualBlock(nn.Module):
     """Two 3x3 conv + norm + ReLU with an optional strided 1x1 projection (`extractor.py:35-90`)."""
+
+    encoder_backward_impl = "aten"  # set by BasicEncoder.forward (see enc_conv / enc_norm_act)
 
     def __init__(self, in_planes: int, planes: int, norm_fn: str = "group", stride: int = 1) -> None:
         super().__init__()
@@ -52,6 +107,13 @@ class ResidualBlock(nn.Module):
             self.downsample = None
 
     def forward(self, x: Tensor) -> Tensor:
+        impl = self.encoder_backward_impl
+        if impl != "aten":
+            y = enc_norm_act(self.norm1, enc_conv(self.conv1, x, impl), True, impl)
+            y = enc_norm_act(self.norm2, enc_conv(self.conv2, y, impl), True, impl)
+            if self.downsample is not None:
+                x = enc_norm_act(self.downsample[1], enc_conv(self.downsample[0], x, impl), False, impl)
+            return self.relu(x + y)
         y = self.relu(self.norm1(self.conv1(x)))
         y = self.relu(self.norm2(self.conv2(y)))
         if self.downsample is not None:
@@ -62,6 +124,8 @@ class ResidualBlock(nn.Module):
 class BasicEncoder(nn.Module):
     """7x7/2 stem (64) -> residual stages 64, 96 (/2), 128 (/2) -> 1x1 to ``output_dim`` at 1/8 resolution
     (`extractor.py:156-231`). A list/tuple input is concatenated on the batch axis and split back after."""
+
+    encoder_backward_impl = "aten"  # set from RAFT.encoder_backward_impl (module docstring)
 
     def __init__(self, output_dim: int = 128, norm_fn: str = "batch", dropout: float = 0.0) -> None:
         super().__init__()
@@ -94,9 +158,18 @@ class BasicEncoder(nn.Module):
         if is_list:
             batch_dim = x[0].shape[0]
             x = torch.cat(list(x), dim=0)
-        x = self.relu1(self.norm1(self.conv1(x)))
+        impl = self.encoder_backward_impl
+        if impl not in ENCODER_BACKWARD_IMPLS:
+            raise ValueError(f"encoder_backward_impl must be 'aten' or 'native', got {impl!r}")
+        for layer in (self.layer1, self.layer2, self.layer3):
+            for blk in layer:
+                blk.encoder_backward_impl = impl
+        if impl != "aten":
+            x = enc_norm_act(self.norm1, enc_conv(self.conv1, x, impl), True, impl)
+        else:
+            x = self.relu1(self.norm1(self.conv1(x)))
         x = self.layer3(self.layer2(self.layer1(x)))
-        x = self.conv2(x)
+        x = enc_conv(self.conv2, x, impl)
         if self.training and self.dropout is not None:
             x = self.dropout(x)
         if is_list:

@@ -120,8 +120,13 @@ class RAFT(nn.Module):
         self.upsample_impl = "native"
         # how autograd on the GPU differentiates the update block's convolutions: "aten" (default): the nn.Conv2d
         # modules (MIOpen); "native": torch.ops.oflow.conv2d_same, the same forward with the dgrad / wgrad kernels of
-        # csrc/conv_backward.hip (fp32 MFMA, no atomics, bit-reproducible). The encoders stay on ATen either way.
+        # csrc/conv_backward.hip (fp32 MFMA, no atomics, bit-reproducible). The encoders have their own switch.
         self.conv_backward_impl = "aten"
+        # how autograd on the GPU differentiates the two encoders, independent of conv_backward_impl: "aten" (default):
+        # the modules (MIOpen); "native": their 32 convolutions as torch.ops.oflow.conv2d_strided and their norm layers
+        # (+ ReLU) as instance_norm_act / frozen_batch_norm_act (extractor.py; csrc/conv_backward.hip,
+        # csrc/norm_backward.hip). cnet's batch norm in train mode (batch statistics) stays the module.
+        self.encoder_backward_impl = "aten"
         self.encoder_streams = True  # cnet beside fnet + the corr pyramid (inference, split encoders)
         self.fnet_streams = True  # with encoder_streams: fnet's image0 and image1 halves on two streams
         # split update loop over >= 2 pairs (CorrBlock): the pairs' two halves run on two streams so that one half's
@@ -190,7 +195,11 @@ class RAFT(nn.Module):
         the last prediction; returns the loss for the caller's ``backward()`` and optimizer. The 1 / 3 / 5 px shares
         the reference logs are kept on ``last_train_metrics``. On the GPU every step autograd differentiates outside
         the convolutions is a native kernel: correlation, convex upsampling, sequence loss; with
-        ``conv_backward_impl = "native"`` the update block's convolutions are too (csrc/conv_backward.hip)."""
+        ``conv_backward_impl = "native"`` the update block's convolutions are too (csrc/conv_backward.hip), and with
+        ``encoder_backward_impl = "native"`` the encoders' convolutions and norm layers (csrc/norm_backward.hip; not
+        batch norm on batch statistics, i.e. cnet in train mode without ``freeze_bn()``). With both and
+        ``alternate_corr=False`` the step's gradients are bit-reproducible; ``alternate_corr=True`` stays outside that
+        claim (its feature gradient sums overlapping windows with atomics)."""
         img0, img1, flow, valid = batch
         flow_predictions = self(img0, img1, iters=self.hparams.iters)
         loss, metrics = sequence_loss(flow_predictions, flow, valid, gamma=self.hparams.gamma)
@@ -381,6 +390,9 @@ class RAFT(nn.Module):
     def _forward(self, image0: Tensor, image1: Tensor, iters: int, flow_init: Optional[Tensor], test_mode: bool):
         if self.conv_backward_impl not in ("aten", "native"):
             raise ValueError(f"conv_backward_impl must be 'aten' or 'native', got {self.conv_backward_impl!r}")
+        if self.encoder_backward_impl not in ("aten", "native"):
+            raise ValueError(f"encoder_backward_impl must be 'aten' or 'native', got {self.encoder_backward_impl!r}")
+        self.fnet.encoder_backward_impl = self.cnet.encoder_backward_impl = self.encoder_backward_impl
         if (NATIVE_NORMALIZE and image0.is_cuda and image1.is_cuda and image0.dtype == image1.dtype == torch.float32
                 and image0.shape == image1.shape
                 and not (torch.is_grad_enabled() and (image0.requires_grad or image1.requires_grad))):

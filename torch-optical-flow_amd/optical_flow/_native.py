@@ -92,6 +92,13 @@ SYMBOLS = (
     "oflow_conv2d_backward_weight_slab_pixels",
     "oflow_conv2d_backward_weight_workspace_floats",
     "oflow_conv2d_backward_weight_f32",
+    "oflow_conv2d_strided_backward_input_f32",
+    "oflow_conv2d_strided_backward_weight_workspace_floats",
+    "oflow_conv2d_strided_backward_weight_f32",
+    "oflow_conv2d_strided_backward_weight_generic_f32",
+    "oflow_instance_norm_backward_f32",
+    "oflow_frozen_batch_norm_backward_workspace_floats",
+    "oflow_frozen_batch_norm_backward_f32",
 )
 
 
@@ -332,6 +339,19 @@ def load() -> ctypes.CDLL:
     lib.oflow_conv2d_backward_weight_workspace_floats.argtypes = [I, I, I, I, I, I, I]
     lib.oflow_conv2d_backward_weight_f32.restype = I
     lib.oflow_conv2d_backward_weight_f32.argtypes = [P, P, I, I, I, I, I, I, I, P, P, P, P]
+    lib.oflow_conv2d_strided_backward_input_f32.restype = I
+    lib.oflow_conv2d_strided_backward_input_f32.argtypes = [P, P, I, I, I, I, I, I, I, I, P, P]
+    lib.oflow_conv2d_strided_backward_weight_workspace_floats.restype = L
+    lib.oflow_conv2d_strided_backward_weight_workspace_floats.argtypes = [I, I, I, I, I, I, I, I]
+    for fn in (lib.oflow_conv2d_strided_backward_weight_f32, lib.oflow_conv2d_strided_backward_weight_generic_f32):
+        fn.restype = I
+        fn.argtypes = [P, P, I, I, I, I, I, I, I, I, P, P, P, P]
+    lib.oflow_instance_norm_backward_f32.restype = I
+    lib.oflow_instance_norm_backward_f32.argtypes = [P, P, I, I, ctypes.c_double, I, P, P]
+    lib.oflow_frozen_batch_norm_backward_workspace_floats.restype = L
+    lib.oflow_frozen_batch_norm_backward_workspace_floats.argtypes = [I, I, I]
+    lib.oflow_frozen_batch_norm_backward_f32.restype = I
+    lib.oflow_frozen_batch_norm_backward_f32.argtypes = [P, P, P, P, P, P, I, I, I, ctypes.c_double, I, P, P, P, P, P]
     v = lib.oflow_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liboflow_hip.so ABI version {v}, expected {ABI_VERSION}: rebuild the library")

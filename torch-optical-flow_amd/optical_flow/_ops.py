@@ -33,6 +33,15 @@ Autograd:
     the weight / bias gradients as pixel-slab partial sums added in a fixed order, all on the fp32 matrix cores: no
     atomics, no MIOpen find step or workspace, bit-reproducible. Only the gradients ``needs_input_grad`` asks for are
     formed (convf1's input, the detached flow, gets none).
+  * ``conv2d_strided`` (the encoders' ``nn.Conv2d`` layers with ``RAFT.encoder_backward_impl = "native"``): as
+    ``conv2d_same`` with stride 1 or 2 (``conv2d_strided_backward``: at stride 2 the input gradient is tiled by the
+    input pixels' parity class, so no matrix-core step is spent on a tap a pixel never meets; with Cin <= 4, the stem,
+    the weight gradient folds (channel, tap) into one tile dimension). The stem's input, the images, gets no gradient.
+  * ``instance_norm_act`` / ``frozen_batch_norm_act`` (the encoders' norm layers with the ReLU that follows them): the
+    forward is the module's own ATen call plus ``relu``; only ``x`` (and the batch norm's parameters and running
+    statistics) are saved, and the backward (csrc/norm_backward.hip) recomputes the statistics and the ReLU mask from
+    it, one workgroup per plane, fixed-order sums in fp64: no atomics, bit-reproducible. Batch norm on batch statistics
+    (train mode) is not covered: those layers stay the module.
 The tiled / NHWC lookups and the raw fp16 on-the-fly ops (``corr_otf_prepare`` / ``corr_lookup_otf``) are the inference
 layouts and have no autograd formula; ``flow_error_stats`` (the metrics' accumulating reduction) has none either, nor
 has ``forward_interpolate`` (the warm-start initialiser, csrc/forward_interpolate.hip: a nearest-landed-source selection
@@ -73,6 +82,12 @@ OPS = (
     "augment_batch",
     "conv2d_same",
     "conv2d_same_backward",
+    "conv2d_strided",
+    "conv2d_strided_backward",
+    "instance_norm_act",
+    "instance_norm_act_backward",
+    "frozen_batch_norm_act",
+    "frozen_batch_norm_act_backward",
 )
 _loaded = False
 
@@ -213,6 +228,47 @@ def _conv_backward(ctx, grad_out):
     return (g_x if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None)
 
 
+def _sconv_setup(ctx, inputs, output):
+    x, weight, bias, stride = inputs
+    ctx.save_for_backward(x, weight)
+    ctx.has_bias = bias is not None
+    ctx.stride = stride
+
+
+def _sconv_backward(ctx, grad_out):
+    x, weight = ctx.saved_tensors
+    need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]), ctx.has_bias and bool(ctx.needs_input_grad[2])]
+    g_x, g_w, g_b = torch.ops.oflow.conv2d_strided_backward(grad_out.contiguous(), x, weight, ctx.stride, need)
+    return (g_x if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None), None
+
+
+def _inorm_setup(ctx, inputs, output):
+    x, eps, relu = inputs
+    ctx.save_for_backward(x)  # the statistics and the ReLU mask are recomputed in the backward: nothing else is kept
+    ctx.args = (eps, relu)
+
+
+def _inorm_backward(ctx, grad_out):
+    (x,) = ctx.saved_tensors
+    eps, relu = ctx.args
+    return torch.ops.oflow.instance_norm_act_backward(grad_out.contiguous(), x, eps, relu), None, None
+
+
+def _fbn_setup(ctx, inputs, output):
+    x, weight, bias, rmean, rvar, eps, relu = inputs
+    ctx.save_for_backward(x, weight, bias, rmean, rvar)
+    ctx.args = (eps, relu)
+
+
+def _fbn_backward(ctx, grad_out):
+    x, weight, bias, rmean, rvar = ctx.saved_tensors
+    eps, relu = ctx.args
+    need = [bool(n) for n in ctx.needs_input_grad[:3]]
+    g_x, g_w, g_b = torch.ops.oflow.frozen_batch_norm_act_backward(grad_out.contiguous(), x, weight, bias, rmean, rvar,
+                                                                   eps, relu, need)
+    return (g_x if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None), None, None, None, None
+
+
 def _alt_setup(ctx, inputs, output):
     _fmap1, _fmap2, f1h, f2h, coords, radius = inputs
     ctx.save_for_backward(f1h, coords, *f2h)  # O(B*C*H*W): the fp32 fmaps are not kept, no volume exists
@@ -239,3 +295,6 @@ def _register_autograd() -> None:
     reg("oflow::convex_upsample", _upsample_backward, setup_context=_upsample_setup)
     reg("oflow::corr_lookup_alt", _alt_backward, setup_context=_alt_setup)
     reg("oflow::conv2d_same", _conv_backward, setup_context=_conv_setup)
+    reg("oflow::conv2d_strided", _sconv_backward, setup_context=_sconv_setup)
+    reg("oflow::instance_norm_act", _inorm_backward, setup_context=_inorm_setup)
+    reg("oflow::frozen_batch_norm_act", _fbn_backward, setup_context=_fbn_setup)
