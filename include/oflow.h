@@ -24,6 +24,8 @@
  *                              autograd (the update block's nn.Conv2d layers in the training step, raft.py:149-175)
  *   oflow_conv2d_strided_backward_*_f32, oflow_instance_norm_backward_f32, oflow_frozen_batch_norm_backward_f32
  *                           <- methods/raft/model/extractor.py:35-231 under autograd (the encoders in the training step)
+ *   oflow_batch_norm_forward_f32, oflow_batch_norm_backward_f32 <- the same file's BatchNorm2d layers on batch statistics
+ *                              (cnet in train mode: the Chairs stage), forward and backward, + the ReLU after them
  *   oflow_flow_stats_f32, oflow_flow2rgb_f32 <- optical_flow/visualization/flow2rgb.py:19-73 (+ visualization/methods/)
  *   oflow_flow_pack_f32     <- optical_flow/io/middlebury.py:43-71, optical_flow/io/pfm.py:79-104 (file payloads)
  *   oflow_flow_error_stats_f32 <- optical_flow/metrics/epe.py:24-65 (AverageEndPointError.update, end_point_error)
@@ -518,6 +520,36 @@ int oflow_frozen_batch_norm_backward_f32(const float* d_grad_out, const float* d
                                          const float* d_running_mean, const float* d_running_var, int B, int C, int HW,
                                          double eps, int relu, float* d_grad_input, float* d_grad_weight, float* d_grad_bias,
                                          float* d_workspace, void* stream);
+
+/*
+ * Batch norm on batch statistics with the ReLU that follows it folded in (relu != 0): nn.BatchNorm2d in train mode,
+ * cnet in the Chairs stage (extractor.py:35-231; csrc/batch_norm.hip). Contiguous fp32 NCHW, HW = H * W, n = B * HW.
+ *   forward:  d_mean[c], d_var[c] (biased) over (B, H, W), formed from fp64 sums shifted by x[0, c, 0, 0] (a constant
+ *             channel has var = 0 exactly); r = 1 / sqrt(var + eps); d_y = (x - mean) * r * weight + bias [ReLU].
+ *             d_y == NULL: statistics only (d_weight, d_bias may then be NULL too). d_mean, d_var (C floats each) and the
+ *             workspace are required. Running statistics are the caller's business (var * n / (n - 1) is the unbiased one).
+ *   backward: takes d_mean and d_var as the forward returned them (it does not recompute them) and recomputes the ReLU
+ *             mask from x with the forward's own arithmetic. g = grad_out * [y > 0] (relu) or grad_out, xh = (x - mean) * r:
+ *             d_grad_bias = sum g, d_grad_weight = sum g * xh,
+ *             d_grad_input = weight * r * (g - d_grad_bias / n - xh * d_grad_weight / n).
+ *             A NULL output is not formed (all three NULL: OFLOW_E_NULL); the others are the same bits whichever are asked
+ *             for. d_grad_input needs both channel sums, so the workspace is required by every backward call.
+ * d_workspace: oflow_batch_norm_workspace_floats(B, C, HW) floats, a function of the shape alone (0 for a shape the calls
+ * refuse), required by both calls and fully written by each; nothing needs zeroing. It holds fp64 partial sums (two per
+ * plane and chunk of oflow_batch_norm_chunk_elements() elements, two per channel), so the pointer must be 8-byte
+ * aligned: otherwise OFLOW_E_ALIGN. Non-positive sizes, eps < 0 or NaN, or B * C * chunks past 2^31 - 1: OFLOW_E_SHAPE.
+ * Nothing is written on an error. No atomics, a fixed summation order: bit-reproducible for a given shape and
+ * alignment (16-byte aligned tensors move as float4, others as scalars).
+ */
+int oflow_batch_norm_chunk_elements(void);
+long long oflow_batch_norm_workspace_floats(int B, int C, int HW);
+int oflow_batch_norm_forward_f32(const float* d_x, const float* d_weight, const float* d_bias, int B, int C, int HW,
+                                 double eps, int relu, float* d_y, float* d_mean, float* d_var, float* d_workspace,
+                                 void* stream);
+int oflow_batch_norm_backward_f32(const float* d_grad_out, const float* d_x, const float* d_weight, const float* d_bias,
+                                  const float* d_mean, const float* d_var, int B, int C, int HW, double eps, int relu,
+                                  float* d_grad_input, float* d_grad_weight, float* d_grad_bias, float* d_workspace,
+                                  void* stream);
 
 /*
  * Backward of the correlation (methods/raft/model/corr.py:38-87 + utils.py:64-80 under autograd, the training step

@@ -31,6 +31,8 @@
 //   conv2d_strided(x, weight, bias?, stride) / conv2d_strided_backward(..., stride, mask3)   the encoders' nn.Conv2d, stride 1 / 2
 //   instance_norm_act(x, eps, relu) / instance_norm_act_backward(grad_out, x, eps, relu)      InstanceNorm2d [+ ReLU] (norm_backward.hip)
 //   frozen_batch_norm_act(x, weight, bias, running_mean, running_var, eps, relu) / _backward(..., mask3)   eval BatchNorm2d [+ ReLU]
+//   batch_norm_act(x, weight, bias, eps, relu) -> (y, mean, var) / batch_norm_act_backward(..., mean, var, eps, relu, mask3)
+//                                                                 train-mode BatchNorm2d [+ ReLU], native both ways (batch_norm.hip)
 //   forward_interpolate(flow) -> Tensor                           warm-start flow_init (upstream RAFT's forward_interpolate)
 //   augment_batch(img1, img2, flow, valid?, params, crop_h, crop_w) -> (img1, img2, flow, valid)   data/augmentor.py:43-324
 #include <array>
@@ -1163,6 +1165,93 @@ Tensor3 frozen_batch_norm_act_backward_meta(const Tensor& go, const Tensor& x, c
   return frozen_batch_norm_act_backward_impl(go, x, w, b, rm, rv, eps, relu, om, false);
 }
 
+// ---------------------------------------------------------------- batch norm on batch statistics (batch_norm.hip)
+void check_bn_batch(const Tensor& x, const Tensor& weight, const Tensor& bias, const Tensor* mean, const Tensor* var,
+                    const char* what) {
+  const char* names[4] = {"weight", "bias", "mean", "var"};
+  const Tensor* ts[4] = {&weight, &bias, mean, var};
+  for (int i = 0; i < 4; ++i)
+    if (ts[i])
+      TORCH_CHECK(ts[i]->dim() == 1 && ts[i]->size(0) == x.size(1) && ts[i]->scalar_type() == at::kFloat &&
+                      ts[i]->device() == x.device(),
+                  what, ": ", names[i], " must be float32 (C) on x's device, got ", ts[i]->scalar_type(), " ", ts[i]->sizes());
+  TORCH_CHECK(x.size(0) <= INT_MAX && x.size(1) <= INT_MAX && x.size(2) * x.size(3) <= INT_MAX, what, ": x ", x.sizes(),
+              " is past the kernels' index range");
+}
+
+// relu(batch_norm(x)) / batch_norm(x) of an nn.BatchNorm2d on batch statistics -> (y, mean, biased var); the running
+// statistics are the caller's to update (extractor.py: enc_norm_act)
+Tensor3 batch_norm_act_impl(const Tensor& x, const Tensor& weight, const Tensor& bias, double eps, bool relu, bool run) {
+  const char* what = "batch_norm_act";
+  if (run) check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
+  check_norm_input(x, what);
+  check_bn_batch(x, weight, bias, nullptr, nullptr, what);
+  const int64_t b = x.size(0), c = x.size(1), hw = x.size(2) * x.size(3);
+  const auto opt = x.options();
+  Tensor y = at::empty(x.sizes(), opt), mean = at::empty({c}, opt), var = at::empty({c}, opt);
+  if (!run) return Tensor3(y, mean, var);
+  if (x.numel() == 0) {  // no elements: no statistics
+    mean.zero_();
+    var.zero_();
+    return Tensor3(y, mean, var);
+  }
+  Tensor xc = x.contiguous(), wc = weight.contiguous(), bc = bias.contiguous();
+  c10::hip::HIPGuardMasqueradingAsCUDA g(xc.device());
+  Tensor ws = at::empty({(int64_t)oflow_batch_norm_workspace_floats((int)b, (int)c, (int)hw)}, opt);
+  check_status(oflow_batch_norm_forward_f32(xc.data_ptr<float>(), wc.data_ptr<float>(), bc.data_ptr<float>(), (int)b, (int)c,
+                                            (int)hw, eps, relu ? 1 : 0, y.data_ptr<float>(), mean.data_ptr<float>(),
+                                            var.data_ptr<float>(), ws.data_ptr<float>(), cur_stream()),
+               what);
+  return Tensor3(y, mean, var);
+}
+Tensor3 batch_norm_act_hip(const Tensor& x, const Tensor& w, const Tensor& b, double eps, bool relu) {
+  return batch_norm_act_impl(x, w, b, eps, relu, true);
+}
+Tensor3 batch_norm_act_meta(const Tensor& x, const Tensor& w, const Tensor& b, double eps, bool relu) {
+  return batch_norm_act_impl(x, w, b, eps, relu, false);
+}
+
+// (grad_x, grad_weight, grad_bias); an output not wanted is an empty (0-element) tensor and is not formed
+Tensor3 batch_norm_act_backward_impl(const Tensor& gout, const Tensor& x, const Tensor& weight, const Tensor& bias,
+                                     const Tensor& mean, const Tensor& var, double eps, bool relu, std::array<bool, 3> om,
+                                     bool run) {
+  const char* what = "batch_norm_act backward";
+  if (run) check_on_gpu(gout, "grad_out", what), check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
+  check_norm_input(x, what);
+  check_bn_batch(x, weight, bias, &mean, &var, what);
+  check_norm_grad(gout, x, what);
+  const int64_t b = x.size(0), c = x.size(1), hw = x.size(2) * x.size(3);
+  const auto opt = x.options();
+  Tensor gx = at::empty(om[0] ? x.sizes() : at::IntArrayRef{0}, opt);
+  Tensor gw = om[1] ? at::empty({c}, opt) : at::empty({0}, opt);
+  Tensor gb = om[2] ? at::empty({c}, opt) : at::empty({0}, opt);
+  if (!run || !(om[0] || om[1] || om[2])) return Tensor3(gx, gw, gb);
+  if (x.numel() == 0) {  // no pixels: the parameter gradients are empty sums
+    if (om[1]) gw.zero_();
+    if (om[2]) gb.zero_();
+    return Tensor3(gx, gw, gb);
+  }
+  Tensor go = gout.contiguous(), xc = x.contiguous();
+  Tensor wc = weight.contiguous(), bc = bias.contiguous(), mc = mean.contiguous(), vc = var.contiguous();
+  c10::hip::HIPGuardMasqueradingAsCUDA g(xc.device());
+  Tensor ws = at::empty({(int64_t)oflow_batch_norm_workspace_floats((int)b, (int)c, (int)hw)}, opt);
+  check_status(oflow_batch_norm_backward_f32(go.data_ptr<float>(), xc.data_ptr<float>(), wc.data_ptr<float>(),
+                                             bc.data_ptr<float>(), mc.data_ptr<float>(), vc.data_ptr<float>(), (int)b, (int)c,
+                                             (int)hw, eps, relu ? 1 : 0, om[0] ? gx.data_ptr<float>() : nullptr,
+                                             om[1] ? gw.data_ptr<float>() : nullptr, om[2] ? gb.data_ptr<float>() : nullptr,
+                                             ws.data_ptr<float>(), cur_stream()),
+               what);
+  return Tensor3(gx, gw, gb);
+}
+Tensor3 batch_norm_act_backward_hip(const Tensor& go, const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& mean,
+                                    const Tensor& var, double eps, bool relu, std::array<bool, 3> om) {
+  return batch_norm_act_backward_impl(go, x, w, b, mean, var, eps, relu, om, true);
+}
+Tensor3 batch_norm_act_backward_meta(const Tensor& go, const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& mean,
+                                     const Tensor& var, double eps, bool relu, std::array<bool, 3> om) {
+  return batch_norm_act_backward_impl(go, x, w, b, mean, var, eps, relu, om, false);
+}
+
 // ---------------------------------------------------------------- warm start (forward_interpolate.hip)
 Tensor forward_interpolate_impl(const Tensor& flow, bool run) {
   const char* what = "forward_interpolate";
@@ -1286,6 +1375,8 @@ TORCH_LIBRARY(oflow, m) {
   m.def("instance_norm_act_backward(Tensor grad_out, Tensor x, float eps, bool relu) -> Tensor");
   m.def("frozen_batch_norm_act(Tensor x, Tensor weight, Tensor bias, Tensor running_mean, Tensor running_var, float eps, bool relu) -> Tensor");
   m.def("frozen_batch_norm_act_backward(Tensor grad_out, Tensor x, Tensor weight, Tensor bias, Tensor running_mean, Tensor running_var, float eps, bool relu, bool[3] output_mask) -> (Tensor, Tensor, Tensor)");
+  m.def("batch_norm_act(Tensor x, Tensor weight, Tensor bias, float eps, bool relu) -> (Tensor y, Tensor mean, Tensor var)");
+  m.def("batch_norm_act_backward(Tensor grad_out, Tensor x, Tensor weight, Tensor bias, Tensor mean, Tensor var, float eps, bool relu, bool[3] output_mask) -> (Tensor, Tensor, Tensor)");
   m.def("forward_interpolate(Tensor flow) -> Tensor");
   m.def("augment_batch(Tensor img1, Tensor img2, Tensor flow, Tensor? valid, Tensor params, int crop_h, int crop_w) -> (Tensor, Tensor, Tensor, Tensor)");
 }
@@ -1319,6 +1410,8 @@ TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
   m.impl("instance_norm_act_backward", &instance_norm_act_backward_hip);
   m.impl("frozen_batch_norm_act", &frozen_batch_norm_act_hip);
   m.impl("frozen_batch_norm_act_backward", &frozen_batch_norm_act_backward_hip);
+  m.impl("batch_norm_act", &batch_norm_act_hip);
+  m.impl("batch_norm_act_backward", &batch_norm_act_backward_hip);
   m.impl("forward_interpolate", &forward_interpolate_hip);
   m.impl("augment_batch", &augment_batch_hip);
 }
@@ -1353,6 +1446,8 @@ TORCH_LIBRARY_IMPL(oflow, CPU, m) {
   m.impl("instance_norm_act_backward", &instance_norm_act_backward_hip);
   m.impl("frozen_batch_norm_act", &frozen_batch_norm_act_hip);
   m.impl("frozen_batch_norm_act_backward", &frozen_batch_norm_act_backward_hip);
+  m.impl("batch_norm_act", &batch_norm_act_hip);
+  m.impl("batch_norm_act_backward", &batch_norm_act_backward_hip);
   m.impl("forward_interpolate", &forward_interpolate_hip);
   m.impl("augment_batch", &augment_batch_hip);
 }
@@ -1386,6 +1481,8 @@ TORCH_LIBRARY_IMPL(oflow, Meta, m) {
   m.impl("instance_norm_act_backward", &instance_norm_act_backward_meta);
   m.impl("frozen_batch_norm_act", &frozen_batch_norm_act_meta);
   m.impl("frozen_batch_norm_act_backward", &frozen_batch_norm_act_backward_meta);
+  m.impl("batch_norm_act", &batch_norm_act_meta);
+  m.impl("batch_norm_act_backward", &batch_norm_act_backward_meta);
   m.impl("forward_interpolate", &forward_interpolate_meta);
   m.impl("augment_batch", &augment_batch_meta);
 }

@@ -13,9 +13,15 @@ Under autograd on the GPU the modules' ``encoder_backward_impl`` (a plain attrib
 block applies directly after it, as ``instance_norm_act`` / ``frozen_batch_norm_act`` (the same forward bit for bit;
 backward csrc/conv_backward.hip and csrc/norm_backward.hip: no atomics, no MIOpen find step, bit-reproducible).
 Eligible norms: ``InstanceNorm2d`` without affine parameters (fnet) and ``BatchNorm2d`` on its running statistics (cnet
-in eval mode / after ``RAFT.freeze_bn()``). Batch norm on batch statistics (cnet in train mode: the Chairs stage) is
-not covered: those 15 layers keep calling the module while cnet's convolutions still go native. ``GroupNorm`` and
-``norm_fn = "none"`` stay the module. CPU tensors, no-grad, autocast and the split inference path are unaffected.
+in eval mode / after ``RAFT.freeze_bn()``). ``GroupNorm`` and ``norm_fn = "none"`` stay the module.
+
+Batch norm on batch statistics (cnet in train mode: the Chairs stage) has a switch of its own, ``batch_norm_impl`` (set
+from ``RAFT.batch_norm_impl``, independent of ``encoder_backward_impl``): "aten" (default) keeps those 15 layers the
+module; "native" records each, with the ReLU after it, as ``torch.ops.oflow.batch_norm_act``, whose forward and backward
+are both csrc/batch_norm.hip. Its forward is not ATen's bit for bit (the statistics are summed in another order), which
+is why it has to be asked for. The module's ``running_mean`` / ``running_var`` / ``num_batches_tracked`` are updated
+after the call as ATen updates them. CPU tensors, no-grad, autocast, eval-mode batch norm and the split inference path
+are unaffected by either switch.
 """
 from __future__ import annotations
 
@@ -45,6 +51,7 @@ def _norm_layer(norm_fn: str, planes: int, groups: int) -> nn.Module:
 
 
 ENCODER_BACKWARD_IMPLS = ("aten", "native")
+BATCH_NORM_IMPLS = ("aten", "native")
 
 
 def _native_autograd(x: Tensor) -> bool:
@@ -69,11 +76,45 @@ def enc_conv(conv: nn.Module, x: Tensor, impl: str = "aten") -> Tensor:
     return conv(x)
 
 
-def enc_norm_act(norm: nn.Module, x: Tensor, relu: bool, impl: str = "aten") -> Tensor:
+def _native_batch_stats(norm: nn.Module, x: Tensor) -> bool:
+    """Whether ``batch_norm_act`` covers this call: a ``BatchNorm2d`` that normalises with batch statistics, affine with
+    fp32 parameters (and fp32 buffers on x's device), a float ``momentum`` (the cumulative average of ``momentum=None``
+    stays the module), more than one value per channel (the module raises its own error otherwise), in the state
+    ``_native_autograd`` describes, with something to differentiate."""
+    if not isinstance(norm, nn.BatchNorm2d) or not _native_autograd(x):
+        return False
+    no_stats = norm.running_mean is None or norm.running_var is None
+    if not no_stats:  # the buffers are updated in place from fp32 statistics on x's device
+        tracked = norm.num_batches_tracked
+        if (norm.running_mean.dtype != torch.float32 or norm.running_var.dtype != torch.float32
+                or norm.running_mean.device != x.device or norm.running_var.device != x.device
+                or (tracked is not None and tracked.device != x.device)):
+            return False
+    return ((norm.training or no_stats) and norm.affine and norm.weight.dtype == torch.float32
+            and norm.bias.dtype == torch.float32 and (no_stats or isinstance(norm.momentum, float))
+            and x.shape[0] * x.shape[2] * x.shape[3] > 1
+            and (x.requires_grad or norm.weight.requires_grad or norm.bias.requires_grad))
+
+
+def enc_norm_act(norm: nn.Module, x: Tensor, relu: bool, impl: str = "aten", bn_impl: str = "aten") -> Tensor:
     """``norm(x)``, through a ReLU when ``relu``; with ``impl`` "native" and an eligible layer (see the module
-    docstring) recorded as one fused op whose backward is native. Anything else calls the module (and ``torch.relu``)."""
+    docstring) recorded as one fused op whose backward is native; with ``bn_impl`` "native" a batch norm on batch
+    statistics as ``batch_norm_act`` (native forward and backward), the module's buffers updated after it. Anything else
+    calls the module (and ``torch.relu``)."""
     if impl not in ENCODER_BACKWARD_IMPLS:
         raise ValueError(f"encoder_backward_impl must be 'aten' or 'native', got {impl!r}")
+    if bn_impl not in BATCH_NORM_IMPLS:
+        raise ValueError(f"batch_norm_impl must be 'aten' or 'native', got {bn_impl!r}")
+    if bn_impl == "native" and _native_batch_stats(norm, x):
+        y, mean, var = _native.ops().batch_norm_act(x, norm.weight, norm.bias, norm.eps, relu)
+        if norm.training and norm.running_mean is not None and norm.running_var is not None:
+            with torch.no_grad():  # ATen's update: the running variance takes the unbiased estimate
+                n, m = x.shape[0] * x.shape[2] * x.shape[3], norm.momentum
+                norm.running_mean.mul_(1 - m).add_(mean, alpha=m)
+                norm.running_var.mul_(1 - m).add_(var, alpha=m * n / (n - 1))
+                if norm.num_batches_tracked is not None:
+                    norm.num_batches_tracked.add_(1)
+        return y
     if impl == "native" and _native_autograd(x):
         if (isinstance(norm, nn.InstanceNorm2d) and not norm.affine and not norm.track_running_stats
                 and x.requires_grad):
@@ -91,6 +132,7 @@ class ResidualBlock(nn.Module):
     """Two 3x3 conv + norm + ReLU with an optional strided 1x1 projection (`extractor.py:35-90`)."""
 
     encoder_backward_impl = "aten"  # set by BasicEncoder.forward (see enc_conv / enc_norm_act)
+    batch_norm_impl = "aten"  # likewise
 
     def __init__(self, in_planes: int, planes: int, norm_fn: str = "group", stride: int = 1) -> None:
         super().__init__()
@@ -107,12 +149,12 @@ class ResidualBlock(nn.Module):
             self.downsample = None
 
     def forward(self, x: Tensor) -> Tensor:
-        impl = self.encoder_backward_impl
-        if impl != "aten":
-            y = enc_norm_act(self.norm1, enc_conv(self.conv1, x, impl), True, impl)
-            y = enc_norm_act(self.norm2, enc_conv(self.conv2, y, impl), True, impl)
+        impl, bn = self.encoder_backward_impl, self.batch_norm_impl
+        if impl != "aten" or bn != "aten":
+            y = enc_norm_act(self.norm1, enc_conv(self.conv1, x, impl), True, impl, bn)
+            y = enc_norm_act(self.norm2, enc_conv(self.conv2, y, impl), True, impl, bn)
             if self.downsample is not None:
-                x = enc_norm_act(self.downsample[1], enc_conv(self.downsample[0], x, impl), False, impl)
+                x = enc_norm_act(self.downsample[1], enc_conv(self.downsample[0], x, impl), False, impl, bn)
             return self.relu(x + y)
         y = self.relu(self.norm1(self.conv1(x)))
         y = self.relu(self.norm2(self.conv2(y)))
@@ -126,6 +168,7 @@ class BasicEncoder(nn.Module):
     (`extractor.py:156-231`). A list/tuple input is concatenated on the batch axis and split back after."""
 
     encoder_backward_impl = "aten"  # set from RAFT.encoder_backward_impl (module docstring)
+    batch_norm_impl = "aten"  # set from RAFT.batch_norm_impl (module docstring)
 
     def __init__(self, output_dim: int = 128, norm_fn: str = "batch", dropout: float = 0.0) -> None:
         super().__init__()
@@ -161,11 +204,14 @@ class BasicEncoder(nn.Module):
         impl = self.encoder_backward_impl
         if impl not in ENCODER_BACKWARD_IMPLS:
             raise ValueError(f"encoder_backward_impl must be 'aten' or 'native', got {impl!r}")
+        bn = self.batch_norm_impl
+        if bn not in BATCH_NORM_IMPLS:
+            raise ValueError(f"batch_norm_impl must be 'aten' or 'native', got {bn!r}")
         for layer in (self.layer1, self.layer2, self.layer3):
             for blk in layer:
-                blk.encoder_backward_impl = impl
-        if impl != "aten":
-            x = enc_norm_act(self.norm1, enc_conv(self.conv1, x, impl), True, impl)
+                blk.encoder_backward_impl, blk.batch_norm_impl = impl, bn
+        if impl != "aten" or bn != "aten":
+            x = enc_norm_act(self.norm1, enc_conv(self.conv1, x, impl), True, impl, bn)
         else:
             x = self.relu1(self.norm1(self.conv1(x)))
         x = self.layer3(self.layer2(self.layer1(x)))

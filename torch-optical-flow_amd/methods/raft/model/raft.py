@@ -125,8 +125,13 @@ class RAFT(nn.Module):
         # how autograd on the GPU differentiates the two encoders, independent of conv_backward_impl: "aten" (default):
         # the modules (MIOpen); "native": their 32 convolutions as torch.ops.oflow.conv2d_strided and their norm layers
         # (+ ReLU) as instance_norm_act / frozen_batch_norm_act (extractor.py; csrc/conv_backward.hip,
-        # csrc/norm_backward.hip). cnet's batch norm in train mode (batch statistics) stays the module.
+        # csrc/norm_backward.hip). cnet's batch norm in train mode (batch statistics) has its own switch, below.
         self.encoder_backward_impl = "aten"
+        # cnet's 15 BatchNorm2d layers on batch statistics (train mode without freeze_bn(): the Chairs stage) under
+        # autograd on the GPU, independent of the two switches above: "aten" (default): the modules (MIOpen);
+        # "native": torch.ops.oflow.batch_norm_act (+ ReLU), forward and backward both csrc/batch_norm.hip. Opt-in
+        # because its forward is not ATen's bit for bit (another summation order for the statistics).
+        self.batch_norm_impl = "aten"
         self.encoder_streams = True  # cnet beside fnet + the corr pyramid (inference, split encoders)
         self.fnet_streams = True  # with encoder_streams: fnet's image0 and image1 halves on two streams
         # split update loop over >= 2 pairs (CorrBlock): the pairs' two halves run on two streams so that one half's
@@ -196,9 +201,10 @@ class RAFT(nn.Module):
         the reference logs are kept on ``last_train_metrics``. On the GPU every step autograd differentiates outside
         the convolutions is a native kernel: correlation, convex upsampling, sequence loss; with
         ``conv_backward_impl = "native"`` the update block's convolutions are too (csrc/conv_backward.hip), and with
-        ``encoder_backward_impl = "native"`` the encoders' convolutions and norm layers (csrc/norm_backward.hip; not
-        batch norm on batch statistics, i.e. cnet in train mode without ``freeze_bn()``). With both and
-        ``alternate_corr=False`` the step's gradients are bit-reproducible; ``alternate_corr=True`` stays outside that
+        ``encoder_backward_impl = "native"`` the encoders' convolutions and norm layers (csrc/norm_backward.hip). Batch
+        norm on batch statistics (cnet in train mode without ``freeze_bn()``) goes native, forward and backward, with
+        ``batch_norm_impl = "native"`` (csrc/batch_norm.hip). With all of them (the third only matters without
+        ``freeze_bn()``) and ``alternate_corr=False`` the step's gradients are bit-reproducible; ``alternate_corr=True`` stays outside that
         claim (its feature gradient sums overlapping windows with atomics)."""
         img0, img1, flow, valid = batch
         flow_predictions = self(img0, img1, iters=self.hparams.iters)
@@ -392,7 +398,10 @@ class RAFT(nn.Module):
             raise ValueError(f"conv_backward_impl must be 'aten' or 'native', got {self.conv_backward_impl!r}")
         if self.encoder_backward_impl not in ("aten", "native"):
             raise ValueError(f"encoder_backward_impl must be 'aten' or 'native', got {self.encoder_backward_impl!r}")
+        if self.batch_norm_impl not in ("aten", "native"):
+            raise ValueError(f"batch_norm_impl must be 'aten' or 'native', got {self.batch_norm_impl!r}")
         self.fnet.encoder_backward_impl = self.cnet.encoder_backward_impl = self.encoder_backward_impl
+        self.fnet.batch_norm_impl = self.cnet.batch_norm_impl = self.batch_norm_impl
         if (NATIVE_NORMALIZE and image0.is_cuda and image1.is_cuda and image0.dtype == image1.dtype == torch.float32
                 and image0.shape == image1.shape
                 and not (torch.is_grad_enabled() and (image0.requires_grad or image1.requires_grad))):

@@ -99,6 +99,10 @@ SYMBOLS = (
     "oflow_instance_norm_backward_f32",
     "oflow_frozen_batch_norm_backward_workspace_floats",
     "oflow_frozen_batch_norm_backward_f32",
+    "oflow_batch_norm_chunk_elements",
+    "oflow_batch_norm_workspace_floats",
+    "oflow_batch_norm_forward_f32",
+    "oflow_batch_norm_backward_f32",
 )
 
 
@@ -352,6 +356,14 @@ def load() -> ctypes.CDLL:
     lib.oflow_frozen_batch_norm_backward_workspace_floats.argtypes = [I, I, I]
     lib.oflow_frozen_batch_norm_backward_f32.restype = I
     lib.oflow_frozen_batch_norm_backward_f32.argtypes = [P, P, P, P, P, P, I, I, I, ctypes.c_double, I, P, P, P, P, P]
+    lib.oflow_batch_norm_chunk_elements.restype = I
+    lib.oflow_batch_norm_chunk_elements.argtypes = []
+    lib.oflow_batch_norm_workspace_floats.restype = L
+    lib.oflow_batch_norm_workspace_floats.argtypes = [I, I, I]
+    lib.oflow_batch_norm_forward_f32.restype = I
+    lib.oflow_batch_norm_forward_f32.argtypes = [P, P, P, I, I, I, ctypes.c_double, I, P, P, P, P, P]
+    lib.oflow_batch_norm_backward_f32.restype = I
+    lib.oflow_batch_norm_backward_f32.argtypes = [P, P, P, P, P, P, I, I, I, ctypes.c_double, I, P, P, P, P, P]
     v = lib.oflow_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liboflow_hip.so ABI version {v}, expected {ABI_VERSION}: rebuild the library")

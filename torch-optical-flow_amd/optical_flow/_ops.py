@@ -40,8 +40,14 @@ Autograd:
   * ``instance_norm_act`` / ``frozen_batch_norm_act`` (the encoders' norm layers with the ReLU that follows them): the
     forward is the module's own ATen call plus ``relu``; only ``x`` (and the batch norm's parameters and running
     statistics) are saved, and the backward (csrc/norm_backward.hip) recomputes the statistics and the ReLU mask from
-    it, one workgroup per plane, fixed-order sums in fp64: no atomics, bit-reproducible. Batch norm on batch statistics
-    (train mode) is not covered: those layers stay the module.
+    it, one workgroup per plane, fixed-order sums in fp64: no atomics, bit-reproducible.
+  * ``batch_norm_act`` (cnet's ``BatchNorm2d`` layers on batch statistics, with the ReLU that follows them, under
+    ``RAFT.batch_norm_impl = "native"``): forward and backward are both native (csrc/batch_norm.hip), because ATen's
+    batch-statistics forward cannot be reproduced bit for bit. It returns (y, mean, biased var); x, the parameters and
+    the two statistics are saved, mean and var are not differentiable, and the backward (``batch_norm_act_backward``)
+    takes the statistics as saved and recomputes the ReLU mask with the forward's arithmetic. One workgroup per
+    (plane, chunk), fp64 partials added in a fixed order: no atomics, bit-reproducible. The op is functional: the
+    module's running statistics are updated by the caller (``model.extractor.enc_norm_act``).
 The tiled / NHWC lookups and the raw fp16 on-the-fly ops (``corr_otf_prepare`` / ``corr_lookup_otf``) are the inference
 layouts and have no autograd formula; ``flow_error_stats`` (the metrics' accumulating reduction) has none either, nor
 has ``forward_interpolate`` (the warm-start initialiser, csrc/forward_interpolate.hip: a nearest-landed-source selection
@@ -88,6 +94,8 @@ OPS = (
     "instance_norm_act_backward",
     "frozen_batch_norm_act",
     "frozen_batch_norm_act_backward",
+    "batch_norm_act",
+    "batch_norm_act_backward",
 )
 _loaded = False
 
@@ -269,6 +277,23 @@ def _fbn_backward(ctx, grad_out):
     return (g_x if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None), None, None, None, None
 
 
+def _bn_setup(ctx, inputs, output):
+    x, weight, bias, eps, relu = inputs
+    _y, mean, var = output
+    ctx.save_for_backward(x, weight, bias, mean, var)  # the statistics as the forward returned them: C floats each
+    ctx.args = (eps, relu)
+    ctx.mark_non_differentiable(mean, var)
+
+
+def _bn_backward(ctx, grad_out, _grad_mean, _grad_var):
+    x, weight, bias, mean, var = ctx.saved_tensors
+    eps, relu = ctx.args
+    need = [bool(n) for n in ctx.needs_input_grad[:3]]
+    g_x, g_w, g_b = torch.ops.oflow.batch_norm_act_backward(grad_out.contiguous(), x, weight, bias, mean, var, eps, relu,
+                                                            need)
+    return (g_x if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None), None, None
+
+
 def _alt_setup(ctx, inputs, output):
     _fmap1, _fmap2, f1h, f2h, coords, radius = inputs
     ctx.save_for_backward(f1h, coords, *f2h)  # O(B*C*H*W): the fp32 fmaps are not kept, no volume exists
@@ -298,3 +323,4 @@ def _register_autograd() -> None:
     reg("oflow::conv2d_strided", _sconv_backward, setup_context=_sconv_setup)
     reg("oflow::instance_norm_act", _inorm_backward, setup_context=_inorm_setup)
     reg("oflow::frozen_batch_norm_act", _fbn_backward, setup_context=_fbn_setup)
+    reg("oflow::batch_norm_act", _bn_backward, setup_context=_bn_setup)
