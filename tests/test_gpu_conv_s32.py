@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_s32_cases as cc
 from optical_flow import _native as N
 from model.corr import CorrBlock
 from model.utils import coords_grid
@@ -28,11 +29,7 @@ def _need_gpu():
     N.load()
 
 
-def _ref(x, w, b, kh, kw):
-    pad = (kh // 2, kw // 2)
-    y = F.conv2d(x.double(), w.double(), None if b is None else b.double(), padding=pad)
-    bound = F.conv2d(x.double().abs(), w.double().abs(), None, padding=pad)
-    return y, bound
+_ref = cc.conv_ref  # float64 convolution and its sum |x||w| bound (shared with test_gpu_conv_s32_tiles.py)
 
 
 def _act(y, act):

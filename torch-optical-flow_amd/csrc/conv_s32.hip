@@ -1194,8 +1194,20 @@ inline dim3 conv_grid(const ConvArgs& a, int bn) {
 // alternated (tools/exp/run_graph_ab.py, profiles/r06/r6s16_ab.log): 17.883 (BD 1) -> 17.720 ms/step, bit-identical
 // (the same MFMAs in the same order; only the loads move). The loop's ISA has no s_waitcnt vmcnt(0) left (7-9 per
 // input group with BD 1).
+// test hook (oflow_exp_last_conv_leaf): the template parameters of the instantiation launched last, 4 bits each from
+// bit 0 except BN's 8: KH, KW, BN (bits 8-15), WM, WN, EPI, TY, AIN, BREG, BD (bits 40-43). Host global, not thread-safe.
+long long g_last_conv_leaf = 0;
+template <int KH, int KW, int BN, int WM, int WN, int EPI, int TY, int AIN, bool BREG, int BD>
+void record_leaf() {
+  static_assert(KH < 16 && KW < 16 && BN < 256 && WM < 16 && WN < 16 && EPI < 16 && TY < 16 && AIN < 16 && BD < 16, "leaf fields");
+  g_last_conv_leaf = (long long)KH | (long long)KW << 4 | (long long)BN << 8 | (long long)WM << 16 | (long long)WN << 20 |
+                     (long long)EPI << 24 | (long long)TY << 28 | (long long)AIN << 32 | (long long)(BREG ? 1 : 0) << 36 |
+                     (long long)BD << 40;
+}
+
 template <int KH, int KW, int BN, int WM, int WN, int EPI, int TY, int AIN>
 void launch_staged(const ConvArgs& a, dim3 grid, hipStream_t s) {
+  record_leaf<KH, KW, BN, WM, WN, EPI, TY, AIN, false, 2>();
   hipLaunchKernelGGL((conv_s32_kernel<KH, KW, BN, WM, WN, EPI, TY, AIN, false, 2>), grid, dim3(64 * WM * WN), 0, s, a);
 }
 
@@ -1205,6 +1217,7 @@ int launch_conv(const ConvArgs& a0, hipStream_t s) {
   if constexpr (BREG) {
     a.tiles_y = (a.H + TY - 1) / TY;
     dim3 grid = conv_grid(a, BN);
+    record_leaf<KH, KW, BN, WM, WN, EPI, TY, kInS32, true, 1>();
     hipLaunchKernelGGL((conv_s32_kernel<KH, KW, BN, WM, WN, EPI, TY, kInS32, true>), grid, dim3(64 * WM * WN), 0, s, a);
     return launch_status();
   } else {
@@ -1504,3 +1517,6 @@ extern "C" void oflow_exp_set_small_grid_px(int pixels) { oflow::g_small_grid_px
 extern "C" void oflow_exp_set_stats_8row(int on) { oflow::g_stats_8row = on; }
 extern "C" void oflow_exp_set_conv_flags(int flags) { oflow::g_conv_exp_flags = flags; }
 extern "C" void oflow_exp_set_bn64_8row(int on) { oflow::g_bn64_8row = on; }
+// test hook (not part of include/oflow.h, not thread-safe): which instantiation the last oflow_conv_s32 call launched,
+// packed as record_leaf() describes (0 before the first launch), so that a test can assert the dispatcher's choice
+extern "C" long long oflow_exp_last_conv_leaf(void) { return oflow::g_last_conv_leaf; }
