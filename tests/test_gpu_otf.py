@@ -3,6 +3,7 @@
 Tolerances: fp16 features (2^-11 relative rounding) with fp32 MFMA accumulation give corr errors of a few 1e-4
 (estimate: sqrt(C)*E|f1 f2|*4e-4/sqrt(C) ~ 5e-4 rms at C=256), so lookup outputs are checked at mean |d| <= 1e-3,
 max |d| <= 2e-2; end-to-end flow at SURVEY §8(c)'s fp16 bar: mean EPE <= 2e-3 px, max <= 2e-2 px.
+The kernels' own arithmetic is held to float64 at the stored fp16 operands in tests/test_gpu_corr_otf_forward.py.
 """
 import numpy as np
 import pytest
