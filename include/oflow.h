@@ -34,6 +34,9 @@
  *                              and its autograd)
  *   oflow_forward_interpolate_f32 <- nothing in the reference: it produces the flow_init that
  *                              methods/raft/model/raft.py:122-123 consumes (upstream RAFT's forward_interpolate)
+ *   oflow_fb_consistency_f32 <- nothing in the reference (csrc/fb_consistency.hip): the forward-backward occlusion
+ *                              mask of a flow pair, UnFlow's criterion (Meister et al., whom the reference cites for
+ *                              optical_flow/visualization/methods/meister.py)
  *   oflow_augment_stats_u8, oflow_augment_dense_f32, oflow_augment_sparse_flow_f32 <- methods/raft/data/augmentor.py:43-324
  *                              (FlowAugmentor, SparseFlowAugmentor: PIL ColorJitter, cv2.resize, eraser, flips, crop)
  *                              + methods/raft/data/dataset.py:114-119 (fp32 flow, the dense valid mask)
@@ -670,6 +673,32 @@ int oflow_sequence_loss_backward_f32(const float* d_grad_out, const float* const
  *   scratch, O((H*W)^2) candidate evaluations per image. B <= 65535, H*W <= 2^30.
  */
 int oflow_forward_interpolate_f32(const float* d_flow, int B, int H, int W, float* d_out, void* stream);
+
+/*
+ * Forward-backward consistency (csrc/fb_consistency.hip): the occlusion masks of a pair of flows in pixel units, and
+ * optionally the squared residuals, in one launch. The criterion is UnFlow's (Meister et al., AAAI 2018; their defaults
+ * alpha = 0.01, beta = 0.5). The reference has no such function.
+ * oflow_fb_consistency_f32: d_fw, d_bw contiguous (B, 2, H, W) fp32, channel 0 = dx, 1 = dy, 4-byte aligned (else
+ *   OFLOW_E_ALIGN); d_mask_* (B, 1, H, W) bytes, written 0 or 1; d_err_* (B, 1, H, W) fp32. For image b, direction d
+ *   (0: a = fw, o = bw, outputs *_fw; 1: a = bw, o = fw, outputs *_bw) and pixel (i, j):
+ *     u = a[b,0,i,j], v = a[b,1,i,j] (fp32);
+ *     px = float(j) + u, py = float(i) + v (fp32 sums, each rounded once);
+ *     inside = px >= 0 && px <= W-1 && py >= 0 && py <= H-1 (false for NaN);
+ *     not inside: mask = 1, err = +inf (the target left the frame, nothing is sampled);
+ *     inside: x0 = floorf(px), x1 = min(x0+1, W-1), wx = px - x0, the same in y; s0, s1 the bilinear values of o[b,0],
+ *       o[b,1] at those four taps in fp32, as top = t00 + wx*(t01 - t00), bot = t10 + wx*(t11 - t10),
+ *       s = top + wy*(bot - top) (products and sums may be contracted into FMAs; a non-finite tap gives NaN in this
+ *       form even under a zero weight);
+ *       err = (u+s0)^2 + (v+s1)^2;  thr = alpha*(u^2 + v^2 + s0^2 + s1^2) + beta;
+ *       mask = !(err <= thr), so non-finite values count as occluded.
+ *   d_mask_fw is required. Direction 1 runs iff d_mask_bw != NULL (d_err_bw without it: OFLOW_E_NULL); d_err_fw and
+ *   d_err_bw may be NULL, and the other outputs are the same bits whichever are asked for. NULL d_fw / d_bw / d_mask_fw:
+ *   OFLOW_E_NULL. B, H or W < 1, B > 65535 or H*W > 2^30: OFLOW_E_SHAPE. An output that overlaps an input or another
+ *   output: OFLOW_E_SHAPE. Every output element is written exactly once, no atomics: bit-identical from run to run.
+ */
+int oflow_fb_consistency_f32(const float* d_fw, const float* d_bw, int B, int H, int W, float alpha, float beta,
+                             unsigned char* d_mask_fw, unsigned char* d_mask_bw, float* d_err_fw, float* d_err_bw,
+                             void* stream);
 
 /*
  * Training-batch augmentation (csrc/augment.hip): the reference's FlowAugmentor / SparseFlowAugmentor

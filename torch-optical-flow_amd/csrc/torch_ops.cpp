@@ -35,6 +35,8 @@
 //                                                                 train-mode BatchNorm2d [+ ReLU], native both ways (batch_norm.hip)
 //   forward_interpolate(flow) -> Tensor                           warm-start flow_init (upstream RAFT's forward_interpolate)
 //   augment_batch(img1, img2, flow, valid?, params, crop_h, crop_w) -> (img1, img2, flow, valid)   data/augmentor.py:43-324
+//   fb_consistency(flow_fw, flow_bw, alpha, beta, both, with_error) -> (mask_fw, mask_bw, err_fw, err_bw)
+//                                                                 forward-backward occlusion masks (not in the reference)
 #include <array>
 #include <torch/library.h>
 #include <ATen/ATen.h>
@@ -1274,8 +1276,43 @@ Tensor forward_interpolate_impl(const Tensor& flow, bool run) {
 Tensor forward_interpolate_hip(const Tensor& flow) { return forward_interpolate_impl(flow, true); }
 Tensor forward_interpolate_meta(const Tensor& flow) { return forward_interpolate_impl(flow, false); }
 
-// ---------------------------------------------------------------- training-batch augmentation (augment.hip)
 using Tensor4 = std::tuple<Tensor, Tensor, Tensor, Tensor>;
+
+// ---------------------------------------------------------------- forward-backward consistency (fb_consistency.hip)
+Tensor4 fb_consistency_impl(const Tensor& fw, const Tensor& bw, double alpha, double beta, bool both, bool with_error,
+                            bool run) {
+  const char* what = "fb_consistency";
+  if (run) check_on_gpu(fw, "flow_fw", what), check_on_gpu(bw, "flow_bw", what);
+  TORCH_CHECK(fw.dim() == 4 && fw.size(1) == 2 && fw.sizes() == bw.sizes(), what, ": flow_fw ", fw.sizes(),
+              " and flow_bw ", bw.sizes(), " must be equal (B, 2, H, W)");
+  TORCH_CHECK(fw.device() == bw.device(), what, ": flow_fw and flow_bw are on different devices");
+  const int64_t b = fw.size(0), h = fw.size(2), w = fw.size(3);
+  TORCH_CHECK(b <= 65535 && h * w <= (int64_t(1) << 30), what, ": flows ", fw.sizes(),
+              " are past the kernel's grid (B <= 65535, H*W <= 2^30)");
+  auto mo = fw.options().dtype(at::kBool), eo = fw.options().dtype(at::kFloat);
+  Tensor none_m = at::empty({0}, mo), none_e = at::empty({0}, eo);
+  Tensor m_fw = at::empty({b, 1, h, w}, mo), m_bw = both ? at::empty({b, 1, h, w}, mo) : none_m;
+  Tensor e_fw = with_error ? at::empty({b, 1, h, w}, eo) : none_e;
+  Tensor e_bw = with_error && both ? at::empty({b, 1, h, w}, eo) : none_e;
+  if (!run || m_fw.numel() == 0) return Tensor4(m_fw, m_bw, e_fw, e_bw);
+  Tensor f = gpu_f32(fw, "flow_fw", what), r = gpu_f32(bw, "flow_bw", what);  // (as warp: any float dtype or strides)
+  c10::hip::HIPGuardMasqueradingAsCUDA g(f.device());
+  check_status(oflow_fb_consistency_f32(f.data_ptr<float>(), r.data_ptr<float>(), (int)b, (int)h, (int)w, (float)alpha,
+                                        (float)beta, reinterpret_cast<unsigned char*>(m_fw.data_ptr<bool>()),
+                                        both ? reinterpret_cast<unsigned char*>(m_bw.data_ptr<bool>()) : nullptr,
+                                        with_error ? e_fw.data_ptr<float>() : nullptr,
+                                        with_error && both ? e_bw.data_ptr<float>() : nullptr, cur_stream()),
+               what);
+  return Tensor4(m_fw, m_bw, e_fw, e_bw);
+}
+Tensor4 fb_consistency_hip(const Tensor& fw, const Tensor& bw, double alpha, double beta, bool both, bool with_error) {
+  return fb_consistency_impl(fw, bw, alpha, beta, both, with_error, true);
+}
+Tensor4 fb_consistency_meta(const Tensor& fw, const Tensor& bw, double alpha, double beta, bool both, bool with_error) {
+  return fb_consistency_impl(fw, bw, alpha, beta, both, with_error, false);
+}
+
+// ---------------------------------------------------------------- training-batch augmentation (augment.hip)
 Tensor4 augment_batch_impl(const Tensor& img1, const Tensor& img2, const Tensor& flow,
                            const c10::optional<Tensor>& valid, const Tensor& params, int64_t ch, int64_t cw,
                            bool run) {
@@ -1379,6 +1416,7 @@ TORCH_LIBRARY(oflow, m) {
   m.def("batch_norm_act_backward(Tensor grad_out, Tensor x, Tensor weight, Tensor bias, Tensor mean, Tensor var, float eps, bool relu, bool[3] output_mask) -> (Tensor, Tensor, Tensor)");
   m.def("forward_interpolate(Tensor flow) -> Tensor");
   m.def("augment_batch(Tensor img1, Tensor img2, Tensor flow, Tensor? valid, Tensor params, int crop_h, int crop_w) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("fb_consistency(Tensor flow_fw, Tensor flow_bw, float alpha, float beta, bool both, bool with_error) -> (Tensor, Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
@@ -1414,6 +1452,7 @@ TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
   m.impl("batch_norm_act_backward", &batch_norm_act_backward_hip);
   m.impl("forward_interpolate", &forward_interpolate_hip);
   m.impl("augment_batch", &augment_batch_hip);
+  m.impl("fb_consistency", &fb_consistency_hip);
 }
 
 // CPU tensors reach the same kernels, whose first check raises "no CPU fallback" (there is no CPU path)
@@ -1450,6 +1489,7 @@ TORCH_LIBRARY_IMPL(oflow, CPU, m) {
   m.impl("batch_norm_act_backward", &batch_norm_act_backward_hip);
   m.impl("forward_interpolate", &forward_interpolate_hip);
   m.impl("augment_batch", &augment_batch_hip);
+  m.impl("fb_consistency", &fb_consistency_hip);
 }
 
 TORCH_LIBRARY_IMPL(oflow, Meta, m) {
@@ -1485,4 +1525,5 @@ TORCH_LIBRARY_IMPL(oflow, Meta, m) {
   m.impl("batch_norm_act_backward", &batch_norm_act_backward_meta);
   m.impl("forward_interpolate", &forward_interpolate_meta);
   m.impl("augment_batch", &augment_batch_meta);
+  m.impl("fb_consistency", &fb_consistency_meta);
 }

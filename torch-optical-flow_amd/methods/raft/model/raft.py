@@ -20,6 +20,9 @@ values; three output-identical changes remove host work from the loop:
     ``coords1 += delta_flow`` update fused into convolution epilogues (``update_impl = "fused"`` selects the
     MIOpen-based ``FusedUpdate`` instead); in test mode the mask head (two convolutions feeding only the
     upsampling) runs at the last iteration only.
+``forward_bidirectional`` (an addition) gives the flows of both directions from one forward, the stacked forward
+``self(cat([image0, image1]), cat([image1, image0]))`` with the feature encoder run once per image; both entry points
+share the encoder stage (``_encode``).
 """
 from __future__ import annotations
 
@@ -362,11 +365,53 @@ class RAFT(nn.Module):
         (``range_guard``) reports an operand that left the fp16 range with RuntimeError: "sync" raises from this
         forward; "deferred" (default) does not wait -- this forward's status is ``last_range_snapshot``
         (``.overflowed()`` waits for it), and a later forward or ``check_range()`` raises for it."""
+        return self._guarded(image0, lambda: self._forward(image0, image1, iters, flow_init, test_mode))
+
+    def forward_bidirectional(
+        self,
+        image0: Tensor,
+        image1: Tensor,
+        iters: int = 12,
+        flow_init: Optional[Tuple[Optional[Tensor], Optional[Tensor]]] = None,
+        test_mode: bool = False,
+    ):
+        """The flow 0 -> 1 and the flow 1 -> 0 of every pair in one forward (an addition): the result of
+        ``self(cat([image0, image1]), cat([image1, image0]), ...)`` split into its halves, with the feature encoder run
+        once per distinct image instead of twice -- fnet's instance norm is per image, so an image's features do not
+        depend on which side of a pair it sits; the reverse direction's correlation pyramid is the forward one's kernel
+        with its arguments swapped, cnet runs on both images, and the update loop sees 2 B independent pairs. Returns
+        ``((low_fw, up_fw), (low_bw, up_bw))`` in test mode, else ``(predictions_fw, predictions_bw)``. ``flow_init``:
+        ``None`` or a pair ``(init_fw, init_bw)``, either ``None`` (zeros). Differentiable wherever ``forward`` is, and
+        under the same range guard. When fnet applies dropout (train mode, ``dropout > 0``) an image's features do depend
+        on its place in the batch, and the stacked forward runs as written above.
+        ``optical_flow.fb_consistency(up_fw, up_bw, both=True)`` turns the two flows into occlusion masks."""
+        n = image0.shape[0]
+        init = None
+        if flow_init is not None:
+            if not isinstance(flow_init, (tuple, list)) or len(flow_init) != 2:
+                raise TypeError("forward_bidirectional: flow_init must be None or a pair (init_fw, init_bw), either of "
+                                "which may be None")
+            init_fw, init_bw = flow_init
+            if init_fw is not None or init_bw is not None:
+                ref = init_fw if init_fw is not None else init_bw
+                init = torch.cat([torch.zeros_like(ref) if t is None else t for t in (init_fw, init_bw)], dim=0)
+        if self.fnet.training and self.fnet.dropout is not None:
+            stacked0, stacked1 = torch.cat([image0, image1], dim=0), torch.cat([image1, image0], dim=0)
+            out = self._guarded(image0, lambda: self._forward(stacked0, stacked1, iters, init, test_mode))
+        else:
+            out = self._guarded(image0, lambda: self._forward(image0, image1, iters, init, test_mode, both=True))
+        if test_mode:
+            low, up = out
+            return (low[:n], up[:n]), (low[n:], up[n:])
+        return [p[:n] for p in out], [p[n:] for p in out]
+
+    def _guarded(self, image0: Tensor, run):
+        """``run()`` under the split-fp16 range guard of ``forward``."""
         guard = self.range_guard in ("sync", "deferred") and image0.is_cuda and not torch.is_grad_enabled()
         capturing = image0.is_cuda and capture_active(image0.device)
         if guard and not capturing:
             self._range_before(image0.device)
-        out = self._forward(image0, image1, iters, flow_init, test_mode)
+        out = run()
         if guard and not capturing:
             self._range_after(image0.device)
         return out
@@ -393,15 +438,11 @@ class RAFT(nn.Module):
         else:
             self._range_pending.append(snap)
 
-    def _forward(self, image0: Tensor, image1: Tensor, iters: int, flow_init: Optional[Tensor], test_mode: bool):
-        if self.conv_backward_impl not in ("aten", "native"):
-            raise ValueError(f"conv_backward_impl must be 'aten' or 'native', got {self.conv_backward_impl!r}")
-        if self.encoder_backward_impl not in ("aten", "native"):
-            raise ValueError(f"encoder_backward_impl must be 'aten' or 'native', got {self.encoder_backward_impl!r}")
-        if self.batch_norm_impl not in ("aten", "native"):
-            raise ValueError(f"batch_norm_impl must be 'aten' or 'native', got {self.batch_norm_impl!r}")
-        self.fnet.encoder_backward_impl = self.cnet.encoder_backward_impl = self.encoder_backward_impl
-        self.fnet.batch_norm_impl = self.cnet.batch_norm_impl = self.batch_norm_impl
+    def _encode(self, image0: Tensor, image1: Tensor, hdim: int, both: bool):
+        """The encoder stage of ``forward`` and ``forward_bidirectional``: input scaling, fnet, the correlation block,
+        cnet. Returns ``(corr_fn, cnet_out, pre_runners, first)``, ``first`` the pairs' first images (cnet's input).
+        ``both``: the pairs are (image0, image1) followed by (image1, image0); fnet still runs once per image, and
+        each side of the correlation block is the two images' features concatenated in that side's order."""
         if (NATIVE_NORMALIZE and image0.is_cuda and image1.is_cuda and image0.dtype == image1.dtype == torch.float32
                 and image0.shape == image1.shape
                 and not (torch.is_grad_enabled() and (image0.requires_grad or image1.requires_grad))):
@@ -410,7 +451,10 @@ class RAFT(nn.Module):
         else:  # CPU tensors, or frames that need gradients (autograd through the elementwise form)
             image0 = (2 * (image0 / 255.0) - 1.0).contiguous()
             image1 = (2 * (image1 / 255.0) - 1.0).contiguous()
-        hdim, cdim = self.hparams.hidden_dim, self.hparams.context_dim
+        first = torch.cat([image0, image1], dim=0) if both else image0
+
+        def sides(a, b):  # an image pair's features -> the two sides of the correlation block
+            return (torch.cat([a, b], dim=0), torch.cat([b, a], dim=0)) if both else (a, b)
 
         # the split encoders implement the inference forward: fnet in train mode with dropout > 0 applies Dropout2d in
         # the reference (extractor.py BasicEncoder.forward), so it then runs as the module (cnet likewise: batch norm)
@@ -429,18 +473,24 @@ class RAFT(nn.Module):
             # runs on a side stream beside fnet and the correlation pyramid, joined before the update loop
             main = torch.cuda.current_stream(image0.device)
             side = _side_stream(image0.device) if self.encoder_streams else None
-            nb = image0.shape[0]
+            ni = image0.shape[0]
+            nb = first.shape[0]  # pairs
             side2 = (_side_stream(image0.device, 1) if side is not None and self.fnet_streams
                      and block is CorrBlock and self.split_corr else None)
             sfi = self.stem_from_image
+            # both directions without stem_from_image: cnet reads the patch rows of both images, so one patch matrix
+            # of both is built first and each of fnet's halves reads its rows of it
+            patches = None if sfi or not both else fnet.stem_patches(first)
             if side2 is not None:
                 # fnet's two images on two streams (instance norm is per image: the same values as one batch), so
                 # three 8-image encoders share the chip and finish together
                 side2.wait_stream(main)
                 with torch.cuda.stream(side2):
-                    f2s = fnet(image1, split_out=True, stem_from_image=sfi)
-                patches = None if sfi else fnet.stem_patches(image0)
-            else:
+                    f2s = fnet(image1, patches=None if patches is None else patches[ni:], split_out=True,
+                               stem_from_image=sfi)
+                if not both:
+                    patches = None if sfi else fnet.stem_patches(image0)
+            elif not both:
                 patches = None if sfi else fnet.stem_patches(torch.cat([image0, image1], dim=0))
             cpatches = None if patches is None else patches[:nb]
             early = (EARLY_LANE_INIT and side is not None and self.fused_update and self.update_impl == "split"
@@ -449,7 +499,7 @@ class RAFT(nn.Module):
             if side is not None:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    cnet_out = cnet(image0, patches=cpatches, stem_from_image=sfi)
+                    cnet_out = cnet(first, patches=cpatches, stem_from_image=sfi)
                     if early:
                         # the lanes' GRU state and context terms depend on cnet only: built here, beside fnet's tail
                         # and the correlation pyramid, instead of after the pyramid on the lanes
@@ -458,23 +508,40 @@ class RAFT(nn.Module):
             if block is CorrBlock and self.split_corr:
                 # features as S32 rows straight from fnet's head conv -> split-fp16 pyramid (no fp32 fmaps)
                 if side2 is not None:
-                    f1s = fnet(image0, patches=patches, split_out=True, stem_from_image=sfi)
+                    f1s = fnet(image0, patches=patches[:ni] if both and patches is not None else patches, split_out=True,
+                               stem_from_image=sfi)
                     main.wait_stream(side2)
                 else:
                     f1s, f2s = fnet([image0, image1], patches=patches, split_out=True, stem_from_image=sfi)
-                corr_fn = CorrBlock.from_split_features(f1s, f2s, radius=self.hparams.corr_radius)
+                corr_fn = CorrBlock.from_split_features(*sides(f1s, f2s), radius=self.hparams.corr_radius)
             else:
                 fmap1, fmap2 = fnet([image0, image1], patches=patches, stem_from_image=sfi)
-                corr_fn = block(fmap1.float(), fmap2.float(), radius=self.hparams.corr_radius)
+                corr_fn = block(*sides(fmap1.float(), fmap2.float()), radius=self.hparams.corr_radius)
             if side is not None:
                 main.wait_stream(side)
             else:
-                cnet_out = cnet(image0, patches=cpatches, stem_from_image=sfi)
+                cnet_out = cnet(first, patches=cpatches, stem_from_image=sfi)
         else:
             fmap1, fmap2 = fnet([image0, image1])
-            corr_fn = block(fmap1.float(), fmap2.float(), radius=self.hparams.corr_radius)
-            cnet_out = cnet(image0)
-        coords0, coords1 = self.initialize_flow(image0)
+            corr_fn = block(*sides(fmap1.float(), fmap2.float()), radius=self.hparams.corr_radius)
+            cnet_out = cnet(first)
+        return corr_fn, cnet_out, pre_runners, first
+
+    def _forward(self, image0: Tensor, image1: Tensor, iters: int, flow_init: Optional[Tensor], test_mode: bool,
+                 both: bool = False):
+        """``forward`` without the range guard. ``both``: the pairs are (image0, image1) followed by (image1, image0),
+        ``forward_bidirectional``'s 2 B pairs, with fnet run once per image; ``flow_init`` then covers the 2 B pairs."""
+        if self.conv_backward_impl not in ("aten", "native"):
+            raise ValueError(f"conv_backward_impl must be 'aten' or 'native', got {self.conv_backward_impl!r}")
+        if self.encoder_backward_impl not in ("aten", "native"):
+            raise ValueError(f"encoder_backward_impl must be 'aten' or 'native', got {self.encoder_backward_impl!r}")
+        if self.batch_norm_impl not in ("aten", "native"):
+            raise ValueError(f"batch_norm_impl must be 'aten' or 'native', got {self.batch_norm_impl!r}")
+        self.fnet.encoder_backward_impl = self.cnet.encoder_backward_impl = self.encoder_backward_impl
+        self.fnet.batch_norm_impl = self.cnet.batch_norm_impl = self.batch_norm_impl
+        hdim, cdim = self.hparams.hidden_dim, self.hparams.context_dim
+        corr_fn, cnet_out, pre_runners, first = self._encode(image0, image1, hdim, both)
+        coords0, coords1 = self.initialize_flow(first)
         if flow_init is not None:
             coords1 = coords1 + flow_init
 

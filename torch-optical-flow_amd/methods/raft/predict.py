@@ -15,6 +15,15 @@ reference keeps an un-indexable glob there), and ``checkpoint=None`` uses the de
 ``warm_start`` (off by default; an addition, RAFT's video mode): the folder is treated as ONE sequence, and every pair
 after the first starts from the previous pair's low-resolution flow projected forward along itself
 (``model.forward_interpolate`` -> ``flow_init``), on the device on the model's stream, with no host sync added.
+
+``bidirectional`` (off by default; an addition): every pair also gets its reverse flow, frame i+1 -> frame i, from the same
+forward (``RAFT.forward_bidirectional``: the feature encoder runs once per frame), written as ``{i:06d}_bw.flo``.
+``occlusion`` (implies ``bidirectional``) also writes the forward-backward occlusion masks of both frames
+(``optical_flow.fb_consistency``, UnFlow's criterion with its default thresholds) as ``{i:06d}_occ.png`` (frame i) and
+``{i:06d}_occ_bw.png`` (frame i+1): 8-bit greyscale, 255 = occluded. They go through the same pinned slots and writer
+thread as the other files. With ``warm_start`` the forward direction is warm-started as above and the reverse direction
+starts cold (its previous pair's reverse flow points the other way along the sequence). Without the two flags the outputs
+are those of before, byte for byte.
 """
 from __future__ import annotations
 
@@ -73,21 +82,34 @@ def image_grid(images: List[Tensor], padding: int = 2) -> Tensor:
     return grid.mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(torch.uint8)
 
 
-def _write_outputs(event: torch.cuda.Event, flo_path: Path, payload: Tensor, png_path: Optional[Path],
-                   grid: Optional[Tensor], range_snapshot=None) -> None:
-    event.synchronize()
-    if range_snapshot is not None and range_snapshot.overflowed():
-        # this pair's forward overflowed a split-fp16 operand: its flow is not valid, so nothing is written for it
-        raise RuntimeError(f"predict: pair {flo_path.stem}: {_native.RANGE_ERROR}")
+def _write_flo(flo_path: Path, payload: Tensor) -> None:
     h, w = payload.shape[:2]
     with open(flo_path, "wb") as f:
         f.write(np.array([MAGIC_NUMBER], np.float32).tobytes())
         f.write(np.array([w, h], np.int32).tobytes())
         f.write(payload.numpy().tobytes())
+
+
+def _write_outputs(event: torch.cuda.Event, flo_path: Path, payload: Tensor, png_path: Optional[Path],
+                   grid: Optional[Tensor], range_snapshot=None, extras=()) -> None:
+    """``extras``: further (path, pinned tensor) files of the pair: a ``.flo`` payload (H, W, 2) fp32 or an 8-bit
+    greyscale ``.png`` (H, W) uint8."""
+    event.synchronize()
+    if range_snapshot is not None and range_snapshot.overflowed():
+        # this pair's forward overflowed a split-fp16 operand: its flow is not valid, so nothing is written for it
+        raise RuntimeError(f"predict: pair {flo_path.stem}: {_native.RANGE_ERROR}")
+    _write_flo(flo_path, payload)
     if png_path is not None:
         from PIL import Image
 
         Image.fromarray(grid.numpy(), "RGB").save(png_path)
+    for path, data in extras:
+        if path.suffix == ".flo":
+            _write_flo(path, data)
+        else:
+            from PIL import Image
+
+            Image.fromarray(data.numpy(), "L").save(path)
 
 
 def main(
@@ -101,6 +123,8 @@ def main(
     eval_mode: bool = False,
     num_workers: int = 4,
     warm_start: bool = False,
+    bidirectional: bool = False,
+    occlusion: bool = False,
 ) -> int:
     """Predict flow for every consecutive pair in ``source`` and write it to ``destination`` (predict.py:39-95).
     ``eval_mode`` puts the model in eval mode; the reference never calls ``.eval()`` (cnet's batch norm then uses
@@ -108,9 +132,13 @@ def main(
     ``warm_start`` treats the folder as one sequence: each pair's low-resolution flow, forward-interpolated on the
     device, initialises the next pair (``flow_init``); the first pair, and a pair whose padded size differs from the
     previous one's, starts cold. Off (the default), every pair starts cold, as in the reference.
+    ``bidirectional`` also writes the reverse flow of every pair (``{i:06d}_bw.flo``) from one shared forward;
+    ``occlusion`` (implies ``bidirectional``) also the occlusion masks of both frames (``{i:06d}_occ.png``,
+    ``{i:06d}_occ_bw.png``; 255 = occluded). The reverse direction is never warm-started.
     Returns the number of pairs written."""
     if iters <= 0:
         raise ValueError("iters must be a positive integer")
+    bidirectional = bidirectional or occlusion
     destination = Path(destination)
     destination.mkdir(parents=True, exist_ok=overwrite)
     dataset = FlowInferenceDataset(source, ext=ext)
@@ -142,7 +170,12 @@ def main(
             flow_init = None
             if prev_low is not None and prev_low.shape[-2:] == (padded0.shape[-2] // 8, padded0.shape[-1] // 8):
                 flow_init = forward_interpolate(prev_low)  # one kernel on the model's stream, no sync
-            low, flow = model(padded0, padded1, iters=iters, flow_init=flow_init, test_mode=True)
+            if bidirectional:
+                (low, flow), (_, flow_bw) = model.forward_bidirectional(
+                    padded0, padded1, iters=iters, flow_init=None if flow_init is None else (flow_init, None),
+                    test_mode=True)
+            else:
+                low, flow = model(padded0, padded1, iters=iters, flow_init=flow_init, test_mode=True)
             if warm_start:
                 prev_low = low
             snap = model.last_range_snapshot  # this pair's own range status, checked by the writer before writing
@@ -153,7 +186,7 @@ def main(
             if slot is not None:
                 slot["future"].result()
             else:
-                slot = slots[i % WRITES_IN_FLIGHT] = {"payload": None, "grid": None, "future": None}
+                slot = slots[i % WRITES_IN_FLIGHT] = dict.fromkeys(("payload", "grid", "payload_bw", "occ", "occ_bw", "future"))
             payload_dev = _native.flow_pack(flow.unsqueeze(0), 2, False)[0]
             payload = _pinned(slot, "payload", payload_dev)
             grid = png = None
@@ -161,9 +194,19 @@ def main(
                 rgb = optical_flow.flow2rgb(flow)
                 grid = _pinned(slot, "grid", image_grid([img0[0] / 255.0, img1[0] / 255.0, rgb]))
                 png = destination / f"{i:06d}.png"
+            extras = []
+            if bidirectional:
+                flow_bw = padder.unpad(flow_bw)[0]
+                extras.append((destination / f"{i:06d}_bw.flo",
+                               _pinned(slot, "payload_bw", _native.flow_pack(flow_bw.unsqueeze(0), 2, False)[0])))
+            if occlusion:
+                occ = optical_flow.fb_consistency(flow.unsqueeze(0), flow_bw.unsqueeze(0), both=True)
+                for key, m in zip(("occ", "occ_bw"), occ):
+                    extras.append((destination / f"{i:06d}_{key}.png", _pinned(slot, key, m[0, 0].to(torch.uint8) * 255)))
             done = torch.cuda.Event()
             done.record()
-            slot["future"] = writer.submit(_write_outputs, done, destination / f"{i:06d}.flo", payload, png, grid, snap)
+            slot["future"] = writer.submit(_write_outputs, done, destination / f"{i:06d}.flo", payload, png, grid, snap,
+                                           tuple(extras))
             count += 1
         for slot in slots:
             if slot is not None:
@@ -199,9 +242,14 @@ def _cli(argv=None) -> int:
     ap.add_argument("--num_workers", type=int, default=4)
     ap.add_argument("--warm_start", action="store_true",
                     help="treat the folder as one sequence: initialise each pair from the previous pair's flow")
+    ap.add_argument("--bidirectional", action="store_true",
+                    help="also write every pair's reverse flow ({i:06d}_bw.flo), from one shared forward")
+    ap.add_argument("--occlusion", action="store_true",
+                    help="implies --bidirectional: also write the forward-backward occlusion masks of both frames "
+                         "({i:06d}_occ.png, {i:06d}_occ_bw.png; 255 = occluded)")
     a = ap.parse_args(argv)
     main(a.source, a.destination, a.checkpoint, a.ext, a.overwrite, a.iters, a.visualize, a.eval_mode, a.num_workers,
-         a.warm_start)
+         a.warm_start, a.bidirectional, a.occlusion)
     return 0
 
 

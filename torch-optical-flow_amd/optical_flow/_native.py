@@ -103,6 +103,7 @@ SYMBOLS = (
     "oflow_batch_norm_workspace_floats",
     "oflow_batch_norm_forward_f32",
     "oflow_batch_norm_backward_f32",
+    "oflow_fb_consistency_f32",
 )
 
 
@@ -364,6 +365,8 @@ def load() -> ctypes.CDLL:
     lib.oflow_batch_norm_forward_f32.argtypes = [P, P, P, I, I, I, ctypes.c_double, I, P, P, P, P, P]
     lib.oflow_batch_norm_backward_f32.restype = I
     lib.oflow_batch_norm_backward_f32.argtypes = [P, P, P, P, P, P, I, I, I, ctypes.c_double, I, P, P, P, P, P]
+    lib.oflow_fb_consistency_f32.restype = I
+    lib.oflow_fb_consistency_f32.argtypes = [P, P, I, I, I, F, F, P, P, P, P, P]
     v = lib.oflow_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liboflow_hip.so ABI version {v}, expected {ABI_VERSION}: rebuild the library")
@@ -579,6 +582,17 @@ def forward_interpolate(flow: torch.Tensor) -> torch.Tensor:
     float64, ties to the lowest source index, zeros when nothing lands. No autograd formula: the input is detached."""
     fl = _tensor(flow, "flow", "forward_interpolate")
     return _run("forward_interpolate", fl.device, ops().forward_interpolate, fl.detach())
+
+
+def fb_consistency(flow_fw: torch.Tensor, flow_bw: torch.Tensor, alpha: float, beta: float, both: bool,
+                   with_error: bool):
+    """The forward-backward occlusion masks of two (B, 2, H, W) flows in pixel units (``torch.ops.oflow.fb_consistency``,
+    include/oflow.h oflow_fb_consistency_f32): (mask_fw, mask_bw, err_fw, err_bw), bool masks (B, 1, H, W) and fp32
+    residuals; the ones not asked for are empty tensors. No autograd formula: the inputs are detached."""
+    what = "fb_consistency"
+    fw, bw = _tensor(flow_fw, "flow_fw", what), _tensor(flow_bw, "flow_bw", what)
+    return _run(what, fw.device, ops().fb_consistency, fw.detach(), bw.detach(), float(alpha), float(beta), bool(both),
+                bool(with_error))
 
 
 AUG_PARAM_DOUBLES = 36  # include/oflow.h OFLOW_AUG_PARAM_DOUBLES

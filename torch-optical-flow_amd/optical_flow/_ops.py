@@ -52,7 +52,10 @@ The tiled / NHWC lookups and the raw fp16 on-the-fly ops (``corr_otf_prepare`` /
 layouts and have no autograd formula; ``flow_error_stats`` (the metrics' accumulating reduction) has none either, nor
 has ``forward_interpolate`` (the warm-start initialiser, csrc/forward_interpolate.hip: a nearest-landed-source selection
 in float64, piecewise constant in its input; callers detach the input, ``model.utils.forward_interpolate``), nor has
-``augment_batch`` (the training-batch augmentation, csrc/augment.hip: integer image levels and a resampled ground truth).
+``augment_batch`` (the training-batch augmentation, csrc/augment.hip: integer image levels and a resampled ground truth),
+nor has ``fb_consistency`` (the forward-backward occlusion masks, csrc/fb_consistency.hip): a mask is piecewise constant
+in the flows and has no gradient, and the residual is returned for inspection and thresholding, not for a loss, so
+``optical_flow.fb_consistency`` detaches its inputs.
 """
 from __future__ import annotations
 
@@ -96,6 +99,7 @@ OPS = (
     "frozen_batch_norm_act_backward",
     "batch_norm_act",
     "batch_norm_act_backward",
+    "fb_consistency",
 )
 _loaded = False
 

@@ -1,3 +1,3 @@
-from .operator import denormalize, integrate, normalize, resize, scale, warp, warp_grid
+from .operator import denormalize, fb_consistency, integrate, normalize, resize, scale, warp, warp_grid
 
-__all__ = ["denormalize", "integrate", "normalize", "resize", "scale", "warp", "warp_grid"]
+__all__ = ["denormalize", "fb_consistency", "integrate", "normalize", "resize", "scale", "warp", "warp_grid"]

@@ -41,6 +41,92 @@ def warp(
     return _native.grid_warp(frame, flow, mode, padding_mode, align_corners)
 
 
+def fb_consistency(
+    flow_fw: Tensor,
+    flow_bw: Tensor,
+    alpha: float = 0.01,
+    beta: float = 0.5,
+    both: bool = False,
+    return_error: bool = False,
+):
+    """Forward-backward consistency check of two flows in pixel units (an addition; the reference has none): the
+    occlusion mask of UnFlow (Meister et al., AAAI 2018, their defaults). A pixel of ``flow_fw``'s frame is occluded when
+    ``flow_bw``, sampled bilinearly where the pixel lands, does not cancel the pixel's own flow:
+    ``|a + s|^2 > alpha * (|a|^2 + |s|^2) + beta``; a pixel that lands outside the frame, and any non-finite value,
+    counts as occluded (include/oflow.h ``oflow_fb_consistency_f32`` states the arithmetic).
+
+    Args:
+        flow_fw: the flow frame 0 -> frame 1, (B, 2, H, W), channel 0 = x
+        flow_bw: the flow frame 1 -> frame 0, same shape and device
+        alpha, beta: the relative and absolute terms of the threshold
+        both: also check ``flow_bw`` against ``flow_fw`` (the mask of frame 1), in the same kernel launch
+        return_error: pair every mask with its squared residual ``|a + s|^2`` (fp32, +inf outside the frame)
+
+    Returns:
+        The bool mask (B, 1, H, W) of ``flow_fw``'s frame, True = occluded; with ``both`` the pair
+        ``(mask_fw, mask_bw)``; with ``return_error`` every mask becomes ``(mask, error)``.
+
+    GPU tensors run one kernel on the current stream (``torch.ops.oflow.fb_consistency``, no host sync); CPU tensors run
+    the same arithmetic as a torch composition. There is no gradient: the inputs are detached.
+    """
+    what = "fb_consistency"
+    for name, t in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
+        if not isinstance(t, Tensor):
+            raise TypeError(f"{what}: {name} must be a torch.Tensor, got {type(t).__name__}")
+        if not t.is_floating_point():
+            raise TypeError(f"{what}: {name} must be a floating-point tensor, got {t.dtype}")
+    if flow_fw.dim() != 4 or flow_fw.shape[1] != 2 or flow_fw.shape != flow_bw.shape:
+        raise ValueError(f"{what}: flow_fw {tuple(flow_fw.shape)} and flow_bw {tuple(flow_bw.shape)} must be equal "
+                         "(B, 2, H, W)")
+    if flow_fw.device != flow_bw.device:
+        raise ValueError(f"{what}: flow_fw and flow_bw are on different devices")
+    fw, bw = flow_fw.detach(), flow_bw.detach()
+    if fw.is_cuda:
+        m_fw, m_bw, e_fw, e_bw = _native.fb_consistency(fw, bw, alpha, beta, both, return_error)
+    else:
+        fw, bw = fw.float().contiguous(), bw.float().contiguous()
+        m_fw, e_fw = _fb_consistency_torch(fw, bw, float(alpha), float(beta))
+        m_bw, e_bw = _fb_consistency_torch(bw, fw, float(alpha), float(beta)) if both else (None, None)
+    first = (m_fw, e_fw) if return_error else m_fw
+    if not both:
+        return first
+    return first, ((m_bw, e_bw) if return_error else m_bw)
+
+
+def _fb_consistency_torch(a: Tensor, o: Tensor, alpha: float, beta: float) -> Tuple[Tensor, Tensor]:
+    """One direction of ``fb_consistency`` on (B, 2, H, W) fp32 tensors in plain torch (the CPU path): the contract of
+    include/oflow.h step by step, every product and sum a separate fp32 operation."""
+    b, _, h, w = a.shape
+    if a.numel() == 0:
+        return a.new_zeros((b, 1, h, w), dtype=torch.bool), a.new_zeros((b, 1, h, w))
+    u, v = a[:, 0], a[:, 1]
+    px = torch.arange(w, dtype=torch.float32).view(1, 1, w) + u
+    py = torch.arange(h, dtype=torch.float32).view(1, h, 1) + v
+    inside = (px >= 0) & (px <= w - 1) & (py >= 0) & (py <= h - 1)
+    pxs, pys = torch.where(inside, px, 0.0), torch.where(inside, py, 0.0)  # (outside: any valid tap, discarded below)
+    fx, fy = torch.floor(pxs), torch.floor(pys)
+    wx, wy = pxs - fx, pys - fy
+    x0, y0 = fx.long(), fy.long()
+    x1, y1 = (x0 + 1).clamp(max=w - 1), (y0 + 1).clamp(max=h - 1)
+
+    def sample(plane: Tensor) -> Tensor:
+        flat = plane.reshape(b, h * w)
+        t00, t01 = flat.gather(1, (y0 * w + x0).view(b, -1)), flat.gather(1, (y0 * w + x1).view(b, -1))
+        t10, t11 = flat.gather(1, (y1 * w + x0).view(b, -1)), flat.gather(1, (y1 * w + x1).view(b, -1))
+        wxf, wyf = wx.reshape(b, -1), wy.reshape(b, -1)
+        top = t00 + wxf * (t01 - t00)
+        bot = t10 + wxf * (t11 - t10)
+        return (top + wyf * (bot - top)).view(b, h, w)
+
+    s0, s1 = sample(o[:, 0]), sample(o[:, 1])
+    du, dv = u + s0, v + s1
+    err = du * du + dv * dv
+    thr = alpha * (u * u + v * v + s0 * s0 + s1 * s1) + beta
+    mask = ~(err <= thr) | ~inside
+    err = torch.where(inside, err, torch.full_like(err, float("inf")))
+    return mask.unsqueeze(1), err.unsqueeze(1)
+
+
 def warp_grid(flow: Tensor) -> Tensor:
     """Sampling grid (B, H, W, 2) = linspace(-1, 1) base grid + normalized flow (B, H, W, 2)
     (`operator.py:36-56`). ``warp`` does not call this: its kernel forms the same grid in registers."""
