@@ -332,9 +332,6 @@ def test_abi_fmap_grad_null_outputs():
     N = 0 is OK and launches nothing."""
     lib = _native.load()
     fn = lib.oflow_corr_fmap_grad_f32
-    fn.restype = ctypes.c_int
-    P, I = ctypes.c_void_p, ctypes.c_int
-    fn.argtypes = [P, P, P, I, I, I, ctypes.c_float, P, P, P]
     b, c, n = 2, 70, 130
     f1, f2 = cc.gaussian(71, (b, c, n)).to(DEV), cc.gaussian(72, (b, c, n)).to(DEV)
     g0 = cc.gaussian(73, (b, n, n)).to(DEV)

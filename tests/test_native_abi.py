@@ -21,6 +21,28 @@ def test_header_and_binding_agree():
     assert _declared_symbols() == sorted(_native.SYMBOLS)
 
 
+def _declared_arity():
+    """name -> number of parameters of every function the header declares (comments stripped, the parenthesised list
+    split on commas, `void` = none; the header has no function-pointer parameters)."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(REPO, "include", "oflow.h")).read(), flags=re.S)
+    arity = {}
+    for name, params in re.findall(r"^\s*(?:[\w*]+\s+)+\**(oflow_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        params = params.strip()
+        arity[name] = 0 if params in ("", "void") else len(params.split(","))
+    return arity
+
+
+def test_every_declared_symbol_has_a_signature_of_the_headers_arity():
+    """A function called through ctypes without argtypes gets its pointers passed as C int."""
+    lib = _native.load()
+    arity = _declared_arity()
+    assert sorted(arity) == _declared_symbols()
+    for name, n in arity.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None, f"{name}: no argtypes declared"
+        assert len(fn.argtypes) == n, f"{name}: {len(fn.argtypes)} argtypes for the header's {n} parameters"
+
+
 def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_native.library_path())
     for name in _declared_symbols():

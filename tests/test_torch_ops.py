@@ -1,9 +1,12 @@
 """``torch.ops.oflow`` (csrc/torch_ops.cpp): the operator library loads on the CPU, registers every op with a Meta
 kernel (what torch.compile's fake tensors run), carries the autograd formulas of optical_flow/_ops.py, and refuses
 CPU tensors. No kernel is launched here; the GPU half (values, torch.compile fullgraph) is in test_gpu_ops.py."""
+import os
+
 import pytest
 import torch
 
+from conftest import REPO
 from optical_flow import _native, _ops
 
 META = torch.device("meta")
@@ -70,16 +73,78 @@ def test_autograd_formulas_are_wired():
     assert g.grad.shape == g.shape
 
 
-def test_cpu_tensors_raise():
+@pytest.mark.parametrize("key", ["CUDA", "CPU", "Meta"])
+def test_every_op_has_a_kernel_for_every_key(key):
+    """The HIP kernel, the CPU kernel (which refuses) and the Meta kernel (torch.compile's) of every op: an op left
+    out of one of them fails only for that op and only on that path."""
     _native.load()
-    x = torch.zeros(1, 8, 16, 16)
-    for call in (
-        lambda: torch.ops.oflow.corr_pyramid(x, x, 2),
-        lambda: torch.ops.oflow.corr_pyramid_tiled(x, x, 2),
-        lambda: torch.ops.oflow.corr_lookup([torch.zeros(256, 1, 16, 16)], torch.zeros(1, 2, 16, 16), 2),
-        lambda: torch.ops.oflow.grid_warp(torch.zeros(1, 3, 4, 4), torch.zeros(1, 2, 4, 4), 0, 0, False),
-        lambda: torch.ops.oflow.grid_sample(torch.zeros(1, 3, 4, 4), torch.zeros(1, 2, 2, 2), 0, 0, False),
-        lambda: torch.ops.oflow.corr_otf_prepare(torch.zeros(1, 32, 8, 8), torch.zeros(1, 32, 8, 8), 1),
-    ):
+    for name in _ops.OPS:
+        assert torch._C._dispatch_has_kernel_for_dispatch_key(f"oflow::{name}", key), (name, key)
+
+
+def test_schemas_are_unchanged():
+    """tests/golden/op_schemas.txt: str(op.default._schema) of every op, recorded before the ops were bound from one
+    function each (names and signatures only)."""
+    _native.load()
+    with open(os.path.join(REPO, "tests", "golden", "op_schemas.txt")) as f:
+        recorded = f.read().splitlines()
+    assert [str(getattr(torch.ops.oflow, name).default._schema) for name in _ops.OPS] == recorded
+
+
+def _cpu_args():
+    """One tiny valid-shaped argument set per op, all on the CPU."""
+    z = torch.zeros
+    f8, f32 = z(1, 8, 16, 16), z(1, 32, 8, 8)
+    co16, co8 = z(1, 2, 16, 16), z(1, 2, 8, 8)
+    tiled = [z(256, int(_native.load().oflow_corr_tiled_level_floats(16, 16)))]
+    f1h, f2h = z(1, 8, 8, 32, dtype=torch.float16), [z(1, 8, 8, 32, dtype=torch.float16)]
+    frame, flow, grid = z(1, 3, 4, 4), z(1, 2, 4, 4), z(1, 2, 2, 2)
+    valid, mask = z(1, 4, 4), z(1, 576, 4, 4)
+    x, w, c4 = z(1, 4, 6, 6), z(8, 4, 3, 3), z(4)
+    img = z(1, 8, 8, 3, dtype=torch.uint8)
+    two, three = [True, True], [True, True, True]
+    return {
+        "corr_pyramid": (f8, f8, 2),
+        "corr_pyramid_tiled": (f8, f8, 2),
+        "corr_lookup": ([z(256, 1, 16, 16)], co16, 2),
+        "corr_lookup_tiled": (tiled, co16, 2),
+        "corr_lookup_tiled_nhwc": (tiled, co16, 2, z(256, 25)),
+        "corr_otf_prepare": (f32, f32, 1),
+        "corr_lookup_otf": (f1h, f2h, co8, 2),
+        "grid_warp": (frame, flow, 0, 0, False),
+        "grid_sample": (frame, grid, 0, 0, False),
+        "corr_lookup_backward": (z(1, 25, 8, 8), co8, 2, 8, 8, 1),
+        "corr_pyramid_backward": ([z(64, 1, 8, 8)], f32, f32),
+        "grid_warp_backward": (z(1, 3, 4, 4), frame, flow, 0, 0, False, two),
+        "grid_sample_backward": (z(1, 3, 2, 2), frame, grid, 0, 0, False, two),
+        "flow_error_stats": (flow, flow, None, 3.0, 0.05, 400.0, z(8, dtype=torch.float64), False),
+        "sequence_loss": ([flow], flow, valid, [1.0], 400.0),
+        "sequence_loss_backward": (torch.ones(()), [flow], flow, valid, [1.0], 400.0, [1]),
+        "convex_upsample": (flow, mask),
+        "convex_upsample_backward": (z(1, 2, 32, 32), flow, mask, two),
+        "corr_lookup_alt": (f32, f32, f1h, f2h, co8, 2),
+        "corr_lookup_alt_backward": (z(1, 25, 8, 8), f1h, f2h, co8, 2, two),
+        "forward_interpolate": (flow,),
+        "augment_batch": (img, img, z(1, 2, 8, 8), None, z(1, _native.AUG_PARAM_DOUBLES, dtype=torch.float64), 4, 4),
+        "conv2d_same": (x, w, None),
+        "conv2d_same_backward": (z(1, 8, 6, 6), x, w, three),
+        "conv2d_strided": (x, w, None, 2),
+        "conv2d_strided_backward": (z(1, 8, 3, 3), x, w, 2, three),
+        "instance_norm_act": (x, 1e-5, True),
+        "instance_norm_act_backward": (x, x, 1e-5, True),
+        "frozen_batch_norm_act": (x, c4, c4, c4, c4, 1e-5, True),
+        "frozen_batch_norm_act_backward": (x, x, c4, c4, c4, c4, 1e-5, True, three),
+        "batch_norm_act": (x, c4, c4, 1e-5, True),
+        "batch_norm_act_backward": (x, x, c4, c4, c4, c4, 1e-5, True, three),
+        "fb_consistency": (flow, flow, 0.01, 0.5, True, False),
+    }
+
+
+def test_cpu_tensors_raise():
+    """Every op refuses CPU tensors with the one "no CPU fallback" message (what each op raised for these arguments
+    before the ops were bound from one function each: all 33 this message, none PyTorch's generic "could not run")."""
+    args = _cpu_args()
+    assert sorted(args) == sorted(_ops.OPS)
+    for name in _ops.OPS:
         with pytest.raises(RuntimeError, match="no CPU fallback"):
-            call()
+            getattr(torch.ops.oflow, name)(*args[name])

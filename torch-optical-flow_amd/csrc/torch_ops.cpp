@@ -5,6 +5,11 @@
 // which is what torch.compile's fake-tensor tracing runs. Autograd formulas are registered from Python
 // (optical_flow/_ops.py) on top of these ops, so CorrBlock / warp trace into a single graph with no breaks.
 //
+// Each op is one function `R op(bool run, Args...)`: with run == false it checks its arguments and returns outputs of
+// the right shape without touching a data pointer (the Meta kernel); with run == true it goes on to the launch (the
+// HIP kernel, and the CPU key's, so that a CPU tensor reaches the "no CPU fallback" check). bind<&op>(m, "name") at
+// the end of the file registers all three from that one function.
+//
 // Ops (reference interface each one implements):
 //   corr_pyramid(fmap1, fmap2, num_levels) -> Tensor[]            CorrBlock.__init__  (corr.py:38-54, 79-87)
 //   corr_pyramid_tiled(fmap1, fmap2, num_levels) -> Tensor[]      same values, tiled lookup layout
@@ -45,7 +50,9 @@
 
 #include <climits>
 #include <cmath>
+#include <initializer_list>
 #include <limits>
+#include <utility>
 #include <vector>
 
 #include "oflow.h"
@@ -53,6 +60,8 @@
 namespace {
 
 using at::Tensor;
+using Tensor3 = std::tuple<Tensor, Tensor, Tensor>;
+using Tensor4 = std::tuple<Tensor, Tensor, Tensor, Tensor>;
 
 void check_status(int st, const char* what) {
   if (st == OFLOW_OK) return;
@@ -63,10 +72,21 @@ void check_status(int st, const char* what) {
 
 void* cur_stream() { return (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(); }
 
+// the one refusal of a tensor that is not on a ROCm GPU (there is no CPU path)
+const char* kNoCpu = "; this MI355X build runs only on ROCm GPU tensors (no CPU fallback)";
+
+void check_on_gpu(const Tensor& t, const char* name, const char* what) {
+  TORCH_CHECK(t.is_cuda(), what, ": ", name, " is on ", t.device(), kNoCpu);
+}
+
 Tensor gpu_f32(const Tensor& t, const char* name, const char* what) {
-  TORCH_CHECK(t.is_cuda(), what, ": ", name, " is on ", t.device(),
-              "; this MI355X build runs only on ROCm GPU tensors (no CPU fallback)");
+  check_on_gpu(t, name, what);
   return t.to(at::kFloat).contiguous();
+}
+
+// a gradient output by its output_mask entry: the given shape where wanted, an empty (0-element) tensor where not
+Tensor wanted(bool want, at::IntArrayRef sizes, const at::TensorOptions& opt) {
+  return at::empty(want ? sizes : at::IntArrayRef{0}, opt);
 }
 
 std::vector<std::pair<int, int>> dims_of(int64_t h, int64_t w, int64_t nl, const char* what) {
@@ -100,16 +120,18 @@ void check_coords(const Tensor& co, const char* what) {
 }
 
 // ---------------------------------------------------------------- pyramid
-std::vector<Tensor> corr_pyramid_hip(const Tensor& fmap1, const Tensor& fmap2, int64_t num_levels) {
+// (check_fmaps has put fmap2 on fmap1's device, so the refusal of a CPU tensor names fmap1)
+std::vector<Tensor> corr_pyramid(bool run, const Tensor& fmap1, const Tensor& fmap2, int64_t num_levels) {
   const char* what = "corr_pyramid";
   check_fmaps(fmap1, fmap2, what);
-  Tensor f1 = gpu_f32(fmap1, "fmap1", what), f2 = gpu_f32(fmap2, "fmap2", what);
-  const int64_t b = f1.size(0), c = f1.size(1), h = f1.size(2), w = f1.size(3);
+  if (run) check_on_gpu(fmap1, "fmap1", what);
+  const int64_t b = fmap1.size(0), c = fmap1.size(1), h = fmap1.size(2), w = fmap1.size(3);
   auto d = dims_of(h, w, num_levels, what);
   std::vector<Tensor> levels;
-  for (auto& p : d) levels.push_back(at::empty({b * h * w, 1, p.first, p.second}, f1.options()));
-  if (b == 0) return levels;
+  for (auto& p : d) levels.push_back(at::empty({b * h * w, 1, p.first, p.second}, fmap1.options().dtype(at::kFloat)));
+  if (!run || b == 0) return levels;
   check_pool_dims(d, num_levels, what);
+  Tensor f1 = gpu_f32(fmap1, "fmap1", what), f2 = gpu_f32(fmap2, "fmap2", what);
   c10::hip::HIPGuardMasqueradingAsCUDA g(f1.device());
   float* ptrs[OFLOW_MAX_LEVELS];
   for (int l = 0; l < num_levels; ++l) ptrs[l] = levels[l].data_ptr<float>();
@@ -119,41 +141,24 @@ std::vector<Tensor> corr_pyramid_hip(const Tensor& fmap1, const Tensor& fmap2, i
   return levels;
 }
 
-std::vector<Tensor> corr_pyramid_meta(const Tensor& fmap1, const Tensor& fmap2, int64_t num_levels) {
-  check_fmaps(fmap1, fmap2, "corr_pyramid");
-  const int64_t b = fmap1.size(0), h = fmap1.size(2), w = fmap1.size(3);
-  std::vector<Tensor> levels;
-  for (auto& p : dims_of(h, w, num_levels, "corr_pyramid"))
-    levels.push_back(at::empty({b * h * w, 1, p.first, p.second}, fmap1.options().dtype(at::kFloat)));
-  return levels;
-}
-
-std::vector<Tensor> corr_pyramid_tiled_hip(const Tensor& fmap1, const Tensor& fmap2, int64_t num_levels) {
+std::vector<Tensor> corr_pyramid_tiled(bool run, const Tensor& fmap1, const Tensor& fmap2, int64_t num_levels) {
   const char* what = "corr_pyramid";
   check_fmaps(fmap1, fmap2, what);
-  Tensor f1 = gpu_f32(fmap1, "fmap1", what), f2 = gpu_f32(fmap2, "fmap2", what);
-  const int64_t b = f1.size(0), c = f1.size(1), h = f1.size(2), w = f1.size(3), q = b * h * w;
+  if (run) check_on_gpu(fmap1, "fmap1", what);
+  const int64_t b = fmap1.size(0), c = fmap1.size(1), h = fmap1.size(2), w = fmap1.size(3), q = b * h * w;
   auto d = dims_of(h, w, num_levels, what);
-  check_pool_dims(d, num_levels, what);
+  if (run) check_pool_dims(d, num_levels, what);
   std::vector<Tensor> levels;
-  for (auto& p : d) levels.push_back(at::empty({q, oflow_corr_tiled_level_floats(p.first, p.second)}, f1.options()));
-  if (q == 0) return levels;
+  for (auto& p : d)
+    levels.push_back(at::empty({q, oflow_corr_tiled_level_floats(p.first, p.second)}, fmap1.options().dtype(at::kFloat)));
+  if (!run || q == 0) return levels;
+  Tensor f1 = gpu_f32(fmap1, "fmap1", what), f2 = gpu_f32(fmap2, "fmap2", what);
   c10::hip::HIPGuardMasqueradingAsCUDA g(f1.device());
   float* ptrs[OFLOW_MAX_LEVELS];
   for (int l = 0; l < num_levels; ++l) ptrs[l] = levels[l].data_ptr<float>();
   check_status(oflow_corr_pyramid_tiled_f32(f1.data_ptr<float>(), f2.data_ptr<float>(), (int)b, (int)c, (int)h,
                                             (int)w, (int)num_levels, ptrs, cur_stream()),
                what);
-  return levels;
-}
-
-std::vector<Tensor> corr_pyramid_tiled_meta(const Tensor& fmap1, const Tensor& fmap2, int64_t num_levels) {
-  check_fmaps(fmap1, fmap2, "corr_pyramid");
-  const int64_t q = fmap1.size(0) * fmap1.size(2) * fmap1.size(3);
-  std::vector<Tensor> levels;
-  for (auto& p : dims_of(fmap1.size(2), fmap1.size(3), num_levels, "corr_pyramid"))
-    levels.push_back(at::empty({q, oflow_corr_tiled_level_floats(p.first, p.second)},
-                               fmap1.options().dtype(at::kFloat)));
   return levels;
 }
 
@@ -212,10 +217,14 @@ Tensor lookup_out(const Tensor& co, int64_t nl, int64_t radius) {
   return at::empty({co.size(0), nl * k * k, co.size(2), co.size(3)}, co.options().dtype(at::kFloat));
 }
 
-Tensor corr_lookup_hip(const std::vector<Tensor>& levels, const Tensor& coords, int64_t radius) {
+// The three lookups over a stored pyramid validate only coords and the radius without run: the levels are checked
+// against the device (tiled_levels asks is_cuda(), which a fake tensor fails) and through their data on the way to
+// the launch.
+Tensor corr_lookup(bool run, const std::vector<Tensor>& levels, const Tensor& coords, int64_t radius) {
   const char* what = "corr_lookup";
   check_coords(coords, what);
   check_radius(radius, OFLOW_MAX_RADIUS, what);
+  if (!run) return lookup_out(coords, (int64_t)levels.size(), radius);
   Tensor co = gpu_f32(coords, "coords", what);
   std::vector<Tensor> keep;
   LevelArgs a = canonical_levels(levels, keep, co, what);
@@ -228,16 +237,11 @@ Tensor corr_lookup_hip(const std::vector<Tensor>& levels, const Tensor& coords, 
   return out;
 }
 
-Tensor corr_lookup_meta(const std::vector<Tensor>& levels, const Tensor& coords, int64_t radius) {
-  check_coords(coords, "corr_lookup");
-  check_radius(radius, OFLOW_MAX_RADIUS, "corr_lookup");
-  return lookup_out(coords, (int64_t)levels.size(), radius);
-}
-
-Tensor corr_lookup_tiled_hip(const std::vector<Tensor>& levels, const Tensor& coords, int64_t radius) {
+Tensor corr_lookup_tiled(bool run, const std::vector<Tensor>& levels, const Tensor& coords, int64_t radius) {
   const char* what = "corr_lookup";
   check_coords(coords, what);
   check_radius(radius, OFLOW_MAX_RADIUS, what);
+  if (!run) return lookup_out(coords, (int64_t)levels.size(), radius);
   Tensor co = gpu_f32(coords, "coords", what);
   LevelArgs a = tiled_levels(levels, co, what);
   Tensor out = lookup_out(co, a.n, radius);
@@ -250,11 +254,12 @@ Tensor corr_lookup_tiled_hip(const std::vector<Tensor>& levels, const Tensor& co
   return out;
 }
 
-void corr_lookup_tiled_nhwc_hip(const std::vector<Tensor>& levels, const Tensor& coords, int64_t radius,
-                                const Tensor& out) {
+void corr_lookup_tiled_nhwc(bool run, const std::vector<Tensor>& levels, const Tensor& coords, int64_t radius,
+                            const Tensor& out) {
   const char* what = "corr_lookup";
   check_coords(coords, what);
   check_radius(radius, OFLOW_MAX_RADIUS, what);
+  if (!run) return;
   Tensor co = gpu_f32(coords, "coords", what);
   LevelArgs a = tiled_levels(levels, co, what);
   const int64_t q = co.size(0) * co.size(2) * co.size(3);
@@ -269,18 +274,12 @@ void corr_lookup_tiled_nhwc_hip(const std::vector<Tensor>& levels, const Tensor&
                what);
 }
 
-void corr_lookup_tiled_nhwc_meta(const std::vector<Tensor>&, const Tensor& coords, int64_t radius, const Tensor&) {
-  check_coords(coords, "corr_lookup");
-  check_radius(radius, OFLOW_MAX_RADIUS, "corr_lookup");
-}
-
 // ---------------------------------------------------------------- on-the-fly (fp16 feature) correlation
-std::tuple<Tensor, std::vector<Tensor>> otf_prepare_impl(const Tensor& fmap1, const Tensor& fmap2, int64_t num_levels,
-                                                         bool run) {
+std::tuple<Tensor, std::vector<Tensor>> corr_otf_prepare(bool run, const Tensor& fmap1, const Tensor& fmap2,
+                                                         int64_t num_levels) {
   const char* what = "corr_otf_prepare";
   check_fmaps(fmap1, fmap2, what);
-  if (run) TORCH_CHECK(fmap1.is_cuda(), what, ": fmap1 is on ", fmap1.device(),
-                       "; this MI355X build runs only on ROCm GPU tensors (no CPU fallback)");
+  if (run) check_on_gpu(fmap1, "fmap1", what);
   const int64_t b = fmap1.size(0), c = fmap1.size(1), h = fmap1.size(2), w = fmap1.size(3);
   TORCH_CHECK(c % 32 == 0, what, ": the fp16 MFMA path needs C % 32 == 0, got C=", c);
   auto d = dims_of(h, w, num_levels, what);
@@ -306,39 +305,47 @@ std::tuple<Tensor, std::vector<Tensor>> otf_prepare_impl(const Tensor& fmap1, co
   return {f1h, f2h};
 }
 
-std::tuple<Tensor, std::vector<Tensor>> otf_prepare_hip(const Tensor& f1, const Tensor& f2, int64_t nl) {
-  return otf_prepare_impl(f1, f2, nl, true);
-}
-std::tuple<Tensor, std::vector<Tensor>> otf_prepare_meta(const Tensor& f1, const Tensor& f2, int64_t nl) {
-  return otf_prepare_impl(f1, f2, nl, false);
-}
-
-Tensor corr_lookup_otf_impl(const Tensor& f1h, const std::vector<Tensor>& f2h, const Tensor& coords, int64_t radius,
-                            bool run) {
-  const char* what = "corr_lookup_otf";
-  check_coords(coords, what);
-  if (run) TORCH_CHECK(coords.is_cuda(), what, ": coords is on ", coords.device(),
-                       "; this MI355X build runs only on ROCm GPU tensors (no CPU fallback)");
-  check_radius(radius, 4, what);
+// f1h (B, H, W, C) fp16 against coords (B, 2, H, W), and the number of fmap2 levels: returns C
+int64_t check_f1h(const Tensor& f1h, int64_t nl, const Tensor& coords, const char* what) {
   const int64_t b = coords.size(0), h = coords.size(2), w = coords.size(3);
   TORCH_CHECK(f1h.scalar_type() == at::kHalf && f1h.dim() == 4 && f1h.size(0) == b && f1h.size(1) == h &&
                   f1h.size(2) == w && f1h.is_contiguous(),
               what, ": f1h ", f1h.sizes(), " must be contiguous fp16 (", b, ", ", h, ", ", w, ", C)");
-  const int64_t c = f1h.size(3), nl = (int64_t)f2h.size();
   TORCH_CHECK(nl >= 1 && nl <= OFLOW_MAX_LEVELS, what, ": number of pyramid levels ", nl, " outside [1, ",
               OFLOW_MAX_LEVELS, "]");
-  const void* ptrs[OFLOW_MAX_LEVELS];
-  int hs[OFLOW_MAX_LEVELS], ws[OFLOW_MAX_LEVELS];
-  for (int64_t i = 0; i < nl; ++i) {
+  return f1h.size(3);
+}
+
+// every fp16 fmap2 level (B, H_l, W_l, C) on the coords' device: fills hs / ws and returns the levels' pixel sum
+int64_t check_f2h_levels(const std::vector<Tensor>& f2h, const Tensor& coords, int64_t c, int* hs, int* ws,
+                         const char* what) {
+  const int64_t b = coords.size(0);
+  int64_t pix = 0;
+  for (int64_t i = 0; i < (int64_t)f2h.size(); ++i) {
     const Tensor& t = f2h[i];
     TORCH_CHECK(t.scalar_type() == at::kHalf && t.dim() == 4 && t.size(0) == b && t.size(3) == c && t.is_contiguous(),
                 what, ": fmap2 level ", i, " ", t.sizes(), " must be contiguous fp16 (", b, ", H_l, W_l, ", c, ")");
     TORCH_CHECK(t.device() == coords.device(), what, ": fmap2 level ", i, " and coords are on different devices");
     hs[i] = (int)t.size(1);
     ws[i] = (int)t.size(2);
+    pix += t.size(1) * t.size(2);
   }
+  return pix;
+}
+
+Tensor corr_lookup_otf(bool run, const Tensor& f1h, const std::vector<Tensor>& f2h, const Tensor& coords,
+                       int64_t radius) {
+  const char* what = "corr_lookup_otf";
+  check_coords(coords, what);
+  if (run) check_on_gpu(coords, "coords", what);
+  check_radius(radius, 4, what);
+  const int64_t b = coords.size(0), h = coords.size(2), w = coords.size(3), nl = (int64_t)f2h.size();
+  const int64_t c = check_f1h(f1h, nl, coords, what);
+  int hs[OFLOW_MAX_LEVELS], ws[OFLOW_MAX_LEVELS];
+  check_f2h_levels(f2h, coords, c, hs, ws, what);
   Tensor out = lookup_out(coords, nl, radius);
   if (!run || out.numel() == 0) return out;
+  const void* ptrs[OFLOW_MAX_LEVELS];
   for (int64_t i = 0; i < nl; ++i) ptrs[i] = f2h[i].data_ptr();  // (fake tensors of a trace have no data pointer)
   Tensor co = gpu_f32(coords, "coords", what);
   c10::hip::HIPGuardMasqueradingAsCUDA g(co.device());
@@ -348,73 +355,44 @@ Tensor corr_lookup_otf_impl(const Tensor& f1h, const std::vector<Tensor>& f2h, c
   return out;
 }
 
-Tensor corr_lookup_otf_hip(const Tensor& f1h, const std::vector<Tensor>& f2h, const Tensor& co, int64_t r) {
-  return corr_lookup_otf_impl(f1h, f2h, co, r, true);
-}
-Tensor corr_lookup_otf_meta(const Tensor& f1h, const std::vector<Tensor>& f2h, const Tensor& co, int64_t r) {
-  return corr_lookup_otf_impl(f1h, f2h, co, r, false);
-}
-
 // corr_lookup_alt: corr_lookup_otf's forward on (f1h, f2h), with the fp32 feature maps those were prepared from as the
 // arguments autograd tracks (their values are not read: the fp16 roundings count as identity, _ops.py).
-void check_alt_fmaps(const Tensor& fmap1, const Tensor& fmap2, const Tensor& f1h, const char* what) {
+Tensor corr_lookup_alt(bool run, const Tensor& fmap1, const Tensor& fmap2, const Tensor& f1h,
+                       const std::vector<Tensor>& f2h, const Tensor& coords, int64_t radius) {
+  const char* what = "corr_lookup_alt";
   check_fmaps(fmap1, fmap2, what);
   TORCH_CHECK(f1h.dim() == 4 && fmap1.size(0) == f1h.size(0) && fmap1.size(1) == f1h.size(3) &&
                   fmap1.size(2) == f1h.size(1) && fmap1.size(3) == f1h.size(2),
               what, ": fmap1 ", fmap1.sizes(), " is not the (B, C, H, W) that f1h ", f1h.sizes(), " (B, H, W, C) was prepared from");
-}
-Tensor corr_lookup_alt_hip(const Tensor& fmap1, const Tensor& fmap2, const Tensor& f1h, const std::vector<Tensor>& f2h,
-                           const Tensor& co, int64_t r) {
-  check_alt_fmaps(fmap1, fmap2, f1h, "corr_lookup_alt");
-  return corr_lookup_otf_impl(f1h, f2h, co, r, true);
-}
-Tensor corr_lookup_alt_meta(const Tensor& fmap1, const Tensor& fmap2, const Tensor& f1h, const std::vector<Tensor>& f2h,
-                            const Tensor& co, int64_t r) {
-  check_alt_fmaps(fmap1, fmap2, f1h, "corr_lookup_alt");
-  return corr_lookup_otf_impl(f1h, f2h, co, r, false);
+  return corr_lookup_otf(run, f1h, f2h, coords, radius);
 }
 
 // (grad_fmap1, grad_fmap2) as (B, C, H, W) fp32; an output not wanted is an empty (0-element) tensor and the kernel gets
 // a null pointer for it (no GEMM / no scratch, no atomics). The per-level NHWC scratch of grad_fmap2 is allocated here:
 // B*C*sum_l H_l*W_l floats, nothing that scales with (HW)^2.
-std::tuple<Tensor, Tensor> corr_lookup_alt_backward_impl(const Tensor& gout, const Tensor& f1h, const std::vector<Tensor>& f2h,
-                                                         const Tensor& coords, int64_t radius, std::array<bool, 2> om,
-                                                         bool run) {
+std::tuple<Tensor, Tensor> corr_lookup_alt_backward(bool run, const Tensor& gout, const Tensor& f1h,
+                                                    const std::vector<Tensor>& f2h, const Tensor& coords,
+                                                    int64_t radius, std::array<bool, 2> om) {
   const char* what = "corr_lookup_alt backward";
   check_coords(coords, what);
   if (run) TORCH_CHECK(coords.is_cuda() && gout.is_cuda(), what, ": coords is on ", coords.device(), ", grad_out on ",
-                       gout.device(), "; this MI355X build runs only on ROCm GPU tensors (no CPU fallback)");
+                       gout.device(), kNoCpu);
   check_radius(radius, 4, what);
-  const int64_t b = coords.size(0), h = coords.size(2), w = coords.size(3);
-  TORCH_CHECK(f1h.scalar_type() == at::kHalf && f1h.dim() == 4 && f1h.size(0) == b && f1h.size(1) == h &&
-                  f1h.size(2) == w && f1h.is_contiguous(),
-              what, ": f1h ", f1h.sizes(), " must be contiguous fp16 (", b, ", ", h, ", ", w, ", C)");
-  const int64_t c = f1h.size(3), nl = (int64_t)f2h.size();
-  TORCH_CHECK(nl >= 1 && nl <= OFLOW_MAX_LEVELS, what, ": number of pyramid levels ", nl, " outside [1, ",
-              OFLOW_MAX_LEVELS, "]");
+  const int64_t b = coords.size(0), h = coords.size(2), w = coords.size(3), nl = (int64_t)f2h.size();
+  const int64_t c = check_f1h(f1h, nl, coords, what);
   const int64_t k = 2 * radius + 1;
   TORCH_CHECK(gout.dim() == 4 && gout.size(0) == b && gout.size(1) == nl * k * k && gout.size(2) == h && gout.size(3) == w,
               what, ": grad_out ", gout.sizes(), " must be (", b, ", ", nl * k * k, ", ", h, ", ", w, ")");
   TORCH_CHECK(gout.device() == coords.device() && f1h.device() == coords.device(), what,
               ": grad_out, f1h and coords are on different devices");
-  const void* ptrs[OFLOW_MAX_LEVELS];
   int hs[OFLOW_MAX_LEVELS], ws[OFLOW_MAX_LEVELS];
-  int64_t pix = 0;
-  for (int64_t i = 0; i < nl; ++i) {
-    const Tensor& t = f2h[i];
-    TORCH_CHECK(t.scalar_type() == at::kHalf && t.dim() == 4 && t.size(0) == b && t.size(3) == c && t.is_contiguous(),
-                what, ": fmap2 level ", i, " ", t.sizes(), " must be contiguous fp16 (", b, ", H_l, W_l, ", c, ")");
-    TORCH_CHECK(t.device() == coords.device(), what, ": fmap2 level ", i, " and coords are on different devices");
-    hs[i] = (int)t.size(1);
-    ws[i] = (int)t.size(2);
-    pix += t.size(1) * t.size(2);
-  }
+  const int64_t pix = check_f2h_levels(f2h, coords, c, hs, ws, what);
   TORCH_CHECK(hs[0] == h && ws[0] == w, what, ": fmap2 level 0 ", f2h[0].sizes(), " must be (", b, ", ", h, ", ", w, ", C)");
   const auto opt = coords.options().dtype(at::kFloat);
-  const std::vector<int64_t> full{b, c, h, w}, none{0};
-  Tensor g1 = at::empty(om[0] ? full : none, opt), g2 = at::empty(om[1] ? full : none, opt);
+  Tensor g1 = wanted(om[0], {b, c, h, w}, opt), g2 = wanted(om[1], {b, c, h, w}, opt);
   if (!run || b * c * h * w == 0 || (!om[0] && !om[1])) return {g1, g2};
   Tensor go = gpu_f32(gout, "grad_out", what), co = gpu_f32(coords, "coords", what);
+  const void* ptrs[OFLOW_MAX_LEVELS];
   for (int64_t i = 0; i < nl; ++i) ptrs[i] = f2h[i].data_ptr();
   c10::hip::HIPGuardMasqueradingAsCUDA g(co.device());
   Tensor scratch = om[1] ? at::empty({b * c * pix}, opt) : at::empty({0}, opt);
@@ -425,14 +403,6 @@ std::tuple<Tensor, Tensor> corr_lookup_alt_backward_impl(const Tensor& gout, con
                                                   om[1] ? scratch.data_ptr<float>() : nullptr, cur_stream()),
                what);
   return {g1, g2};
-}
-std::tuple<Tensor, Tensor> corr_lookup_alt_backward_hip(const Tensor& go, const Tensor& f1h, const std::vector<Tensor>& f2h,
-                                                        const Tensor& co, int64_t r, std::array<bool, 2> om) {
-  return corr_lookup_alt_backward_impl(go, f1h, f2h, co, r, om, true);
-}
-std::tuple<Tensor, Tensor> corr_lookup_alt_backward_meta(const Tensor& go, const Tensor& f1h, const std::vector<Tensor>& f2h,
-                                                         const Tensor& co, int64_t r, std::array<bool, 2> om) {
-  return corr_lookup_alt_backward_impl(go, f1h, f2h, co, r, om, false);
 }
 
 // ---------------------------------------------------------------- warp / grid_sample
@@ -448,10 +418,11 @@ void check_warp(const Tensor& fr, const Tensor& fl, const char* what) {
   TORCH_CHECK(fr.device() == fl.device(), what, ": frame and flow are on different devices");
 }
 
-Tensor grid_warp_hip(const Tensor& frame, const Tensor& flow, int64_t mode, int64_t pad, bool align_corners) {
+Tensor grid_warp(bool run, const Tensor& frame, const Tensor& flow, int64_t mode, int64_t pad, bool align_corners) {
   const char* what = "warp";
   check_modes(mode, pad, what);
   check_warp(frame, flow, what);
+  if (!run) return at::empty(frame.sizes(), frame.options().dtype(at::kFloat));
   Tensor fr = gpu_f32(frame, "frame", what), fl = gpu_f32(flow, "flow", what);
   Tensor out = at::empty_like(fr);
   if (out.numel() == 0) return out;
@@ -463,22 +434,18 @@ Tensor grid_warp_hip(const Tensor& frame, const Tensor& flow, int64_t mode, int6
   return out;
 }
 
-Tensor grid_warp_meta(const Tensor& frame, const Tensor& flow, int64_t mode, int64_t pad, bool) {
-  check_modes(mode, pad, "warp");
-  check_warp(frame, flow, "warp");
-  return at::empty(frame.sizes(), frame.options().dtype(at::kFloat));
-}
-
 void check_sample(const Tensor& x, const Tensor& g, const char* what) {
   TORCH_CHECK(x.dim() == 4 && g.dim() == 4 && g.size(3) == 2 && g.size(0) == x.size(0), what, ": input ", x.sizes(),
               " must be (B, C, H, W) and grid ", g.sizes(), " (B, Ho, Wo, 2)");
   TORCH_CHECK(x.device() == g.device(), what, ": input and grid are on different devices");
 }
 
-Tensor grid_sample_hip(const Tensor& input, const Tensor& grid, int64_t mode, int64_t pad, bool align_corners) {
+Tensor grid_sample(bool run, const Tensor& input, const Tensor& grid, int64_t mode, int64_t pad, bool align_corners) {
   const char* what = "grid_sample";
   check_modes(mode, pad, what);
   check_sample(input, grid, what);
+  if (!run)
+    return at::empty({input.size(0), input.size(1), grid.size(1), grid.size(2)}, input.options().dtype(at::kFloat));
   Tensor x = gpu_f32(input, "input", what), gr = gpu_f32(grid, "grid", what);
   Tensor out = at::empty({x.size(0), x.size(1), gr.size(1), gr.size(2)}, x.options());
   if (out.numel() == 0) return out;
@@ -490,24 +457,17 @@ Tensor grid_sample_hip(const Tensor& input, const Tensor& grid, int64_t mode, in
   return out;
 }
 
-Tensor grid_sample_meta(const Tensor& input, const Tensor& grid, int64_t mode, int64_t pad, bool) {
-  check_modes(mode, pad, "grid_sample");
-  check_sample(input, grid, "grid_sample");
-  return at::empty({input.size(0), input.size(1), grid.size(1), grid.size(2)}, input.options().dtype(at::kFloat));
-}
-
 // warp / grid_sample backward (warp_backward.hip): (grad_frame, grad_flow) / (grad_input, grad_grid)
 // output_mask (ATen grid_sampler_2d_backward's): an output not wanted is returned as an empty (0-element) tensor and
 // the kernel gets a null pointer for it (no zero fill, no atomics for grad_frame)
-std::tuple<Tensor, Tensor> grid_warp_backward_impl(const Tensor& gout, const Tensor& frame, const Tensor& flow,
-                                                   int64_t mode, int64_t pad, bool ac, std::array<bool, 2> mask, bool run) {
+std::tuple<Tensor, Tensor> grid_warp_backward(bool run, const Tensor& gout, const Tensor& frame, const Tensor& flow,
+                                              int64_t mode, int64_t pad, bool ac, std::array<bool, 2> mask) {
   const char* what = "warp backward";
   check_modes(mode, pad, what);
   check_warp(frame, flow, what);
   TORCH_CHECK(gout.sizes() == frame.sizes(), what, ": grad_out ", gout.sizes(), " must match the frame ", frame.sizes());
   const auto fopt = frame.options().dtype(at::kFloat), lopt = flow.options().dtype(at::kFloat);
-  if (!run)
-    return {at::empty(mask[0] ? frame.sizes() : at::IntArrayRef{0}, fopt), at::empty(mask[1] ? flow.sizes() : at::IntArrayRef{0}, lopt)};
+  if (!run) return {wanted(mask[0], frame.sizes(), fopt), wanted(mask[1], flow.sizes(), lopt)};
   Tensor go = gpu_f32(gout, "grad_out", what), fr = gpu_f32(frame, "frame", what), fl = gpu_f32(flow, "flow", what);
   Tensor gfr = mask[0] ? at::zeros_like(fr) : at::empty({0}, fopt), gfl = mask[1] ? at::empty_like(fl) : at::empty({0}, lopt);
   if (fr.numel() == 0) return {gfr, gfl.zero_()};
@@ -520,17 +480,9 @@ std::tuple<Tensor, Tensor> grid_warp_backward_impl(const Tensor& gout, const Ten
                what);
   return {gfr, gfl};
 }
-std::tuple<Tensor, Tensor> grid_warp_backward_hip(const Tensor& go, const Tensor& fr, const Tensor& fl, int64_t m, int64_t p, bool ac,
-                                                  std::array<bool, 2> mask) {
-  return grid_warp_backward_impl(go, fr, fl, m, p, ac, mask, true);
-}
-std::tuple<Tensor, Tensor> grid_warp_backward_meta(const Tensor& go, const Tensor& fr, const Tensor& fl, int64_t m, int64_t p, bool ac,
-                                                   std::array<bool, 2> mask) {
-  return grid_warp_backward_impl(go, fr, fl, m, p, ac, mask, false);
-}
 
-std::tuple<Tensor, Tensor> grid_sample_backward_impl(const Tensor& gout, const Tensor& input, const Tensor& grid,
-                                                     int64_t mode, int64_t pad, bool ac, std::array<bool, 2> mask, bool run) {
+std::tuple<Tensor, Tensor> grid_sample_backward(bool run, const Tensor& gout, const Tensor& input, const Tensor& grid,
+                                                int64_t mode, int64_t pad, bool ac, std::array<bool, 2> mask) {
   const char* what = "grid_sample backward";
   check_modes(mode, pad, what);
   check_sample(input, grid, what);
@@ -538,8 +490,7 @@ std::tuple<Tensor, Tensor> grid_sample_backward_impl(const Tensor& gout, const T
                   gout.size(2) == grid.size(1) && gout.size(3) == grid.size(2),
               what, ": grad_out ", gout.sizes(), " must be (B, C, Ho, Wo)");
   const auto xopt = input.options().dtype(at::kFloat), gopt = grid.options().dtype(at::kFloat);
-  if (!run)
-    return {at::empty(mask[0] ? input.sizes() : at::IntArrayRef{0}, xopt), at::empty(mask[1] ? grid.sizes() : at::IntArrayRef{0}, gopt)};
+  if (!run) return {wanted(mask[0], input.sizes(), xopt), wanted(mask[1], grid.sizes(), gopt)};
   Tensor go = gpu_f32(gout, "grad_out", what), x = gpu_f32(input, "input", what), gr = gpu_f32(grid, "grid", what);
   Tensor gx = mask[0] ? at::zeros_like(x) : at::empty({0}, xopt), gg = mask[1] ? at::empty_like(gr) : at::empty({0}, gopt);
   if (go.numel() == 0) return {gx, gg.zero_()};
@@ -552,18 +503,10 @@ std::tuple<Tensor, Tensor> grid_sample_backward_impl(const Tensor& gout, const T
                what);
   return {gx, gg};
 }
-std::tuple<Tensor, Tensor> grid_sample_backward_hip(const Tensor& go, const Tensor& x, const Tensor& gr, int64_t m, int64_t p, bool ac,
-                                                    std::array<bool, 2> mask) {
-  return grid_sample_backward_impl(go, x, gr, m, p, ac, mask, true);
-}
-std::tuple<Tensor, Tensor> grid_sample_backward_meta(const Tensor& go, const Tensor& x, const Tensor& gr, int64_t m, int64_t p, bool ac,
-                                                     std::array<bool, 2> mask) {
-  return grid_sample_backward_impl(go, x, gr, m, p, ac, mask, false);
-}
 
 // ---------------------------------------------------------------- backward (training path, §8(f) row 3)
-std::vector<Tensor> lookup_backward_impl(const Tensor& grad_out, const Tensor& coords, int64_t radius, int64_t h0,
-                                         int64_t w0, int64_t nl, bool run) {
+std::vector<Tensor> corr_lookup_backward(bool run, const Tensor& grad_out, const Tensor& coords, int64_t radius,
+                                         int64_t h0, int64_t w0, int64_t nl) {
   const char* what = "corr_lookup_backward";
   check_coords(coords, what);
   check_radius(radius, OFLOW_MAX_RADIUS, what);
@@ -572,8 +515,7 @@ std::vector<Tensor> lookup_backward_impl(const Tensor& grad_out, const Tensor& c
                   grad_out.size(3) == w,
               what, ": grad_out ", grad_out.sizes(), " does not match coords / levels");
   auto d = dims_of(h0, w0, nl, what);
-  if (run) TORCH_CHECK(coords.is_cuda(), what, ": coords is on ", coords.device(),
-                       "; this MI355X build runs only on ROCm GPU tensors (no CPU fallback)");
+  if (run) check_on_gpu(coords, "coords", what);
   std::vector<Tensor> grads;
   auto opt = coords.options().dtype(at::kFloat);
   for (auto& p : d) grads.push_back(run ? at::zeros({b * h * w, 1, p.first, p.second}, opt)
@@ -594,20 +536,11 @@ std::vector<Tensor> lookup_backward_impl(const Tensor& grad_out, const Tensor& c
   return grads;
 }
 
-std::vector<Tensor> lookup_backward_hip(const Tensor& go, const Tensor& co, int64_t r, int64_t h0, int64_t w0,
-                                        int64_t nl) {
-  return lookup_backward_impl(go, co, r, h0, w0, nl, true);
-}
-std::vector<Tensor> lookup_backward_meta(const Tensor& go, const Tensor& co, int64_t r, int64_t h0, int64_t w0,
-                                         int64_t nl) {
-  return lookup_backward_impl(go, co, r, h0, w0, nl, false);
-}
-
 // grads[0] += every coarser level's gradient pushed back through the floor 2x2 pools (native kernel), then
 // grad_f1 = f2 . G^T / sqrt(C), grad_f2 = f1 . G / sqrt(C) as batched GEMMs on the fp32 matrix cores
 // (oflow_corr_fmap_grad_f32, csrc/corr_backward.hip)
-std::tuple<Tensor, Tensor> pyramid_backward_impl(const std::vector<Tensor>& level_grads, const Tensor& fmap1,
-                                                 const Tensor& fmap2, bool run) {
+std::tuple<Tensor, Tensor> corr_pyramid_backward(bool run, const std::vector<Tensor>& level_grads, const Tensor& fmap1,
+                                                 const Tensor& fmap2) {
   const char* what = "corr_pyramid_backward";
   check_fmaps(fmap1, fmap2, what);
   const int64_t b = fmap1.size(0), c = fmap1.size(1), h = fmap1.size(2), w = fmap1.size(3), n = h * w;
@@ -642,16 +575,7 @@ std::tuple<Tensor, Tensor> pyramid_backward_impl(const std::vector<Tensor>& leve
   return {g1.to(fmap1.scalar_type()), g2.to(fmap2.scalar_type())};
 }
 
-std::tuple<Tensor, Tensor> pyramid_backward_hip(const std::vector<Tensor>& g, const Tensor& f1, const Tensor& f2) {
-  return pyramid_backward_impl(g, f1, f2, true);
-}
-std::tuple<Tensor, Tensor> pyramid_backward_meta(const std::vector<Tensor>& g, const Tensor& f1, const Tensor& f2) {
-  return pyramid_backward_impl(g, f1, f2, false);
-}
-
 // ---------------------------------------------------------------- metrics / sequence loss (flow_metrics.hip)
-const char* kNoCpu = "; this MI355X build runs only on ROCm GPU tensors (no CPU fallback)";
-
 void check_flow_pair(const Tensor& pred, const Tensor& target, const char* what) {
   TORCH_CHECK(pred.dim() == 4 && pred.size(1) == 2 && pred.sizes() == target.sizes(), what, ": pred ", pred.sizes(),
               " and target ", target.sizes(), " must be equal (B, 2, H, W)");
@@ -694,8 +618,8 @@ ValidArg valid_arg(const Tensor& valid, const Tensor& flow, bool need_contiguous
   return a;
 }
 
-Tensor flow_error_stats_impl(const Tensor& pred, const Tensor& target, const c10::optional<Tensor>& valid, double abs_t,
-                             double rel_t, double max_flow, const Tensor& accum, bool epe_map, bool run) {
+Tensor flow_error_stats(bool run, const Tensor& pred, const Tensor& target, const c10::optional<Tensor>& valid,
+                        double abs_t, double rel_t, double max_flow, const Tensor& accum, bool epe_map) {
   const char* what = "flow_error_stats";
   check_flow_pair(pred, target, what);
   if (valid.has_value()) check_valid(*valid, pred, what);
@@ -703,11 +627,9 @@ Tensor flow_error_stats_impl(const Tensor& pred, const Tensor& target, const c10
                   accum.device() == pred.device(),
               what, ": the accumulator must be a contiguous float64 [8] on the flow's device, got ", accum.sizes());
   const int64_t b = pred.size(0), h = pred.size(2), w = pred.size(3);
-  const auto fopt = pred.options().dtype(at::kFloat);
-  if (!run) return epe_map ? at::empty({b, h, w}, fopt) : at::empty({0}, fopt);
-  TORCH_CHECK(pred.is_cuda(), what, ": pred is on ", pred.device(), kNoCpu);
-  Tensor map = epe_map ? at::empty({b, h, w}, fopt) : at::empty({0}, fopt);
-  if (b * h * w == 0) return map;
+  if (run) check_on_gpu(pred, "pred", what);
+  Tensor map = wanted(epe_map, {b, h, w}, pred.options().dtype(at::kFloat));
+  if (!run || b * h * w == 0) return map;
   Tensor pr = strided_f32(pred), tg = strided_f32(target);
   ValidArg va;
   if (valid.has_value()) va = valid_arg(*valid, pr, false);
@@ -721,14 +643,6 @@ Tensor flow_error_stats_impl(const Tensor& pred, const Tensor& target, const c10
                what);
   return map;
 }
-Tensor flow_error_stats_hip(const Tensor& p, const Tensor& t, const c10::optional<Tensor>& v, double a, double r, double m,
-                            const Tensor& acc, bool map) {
-  return flow_error_stats_impl(p, t, v, a, r, m, acc, map, true);
-}
-Tensor flow_error_stats_meta(const Tensor& p, const Tensor& t, const c10::optional<Tensor>& v, double a, double r, double m,
-                             const Tensor& acc, bool map) {
-  return flow_error_stats_impl(p, t, v, a, r, m, acc, map, false);
-}
 
 void check_loss_args(const std::vector<Tensor>& preds, const Tensor& gt, const Tensor& valid, at::ArrayRef<double> weights,
                      const char* what) {
@@ -739,13 +653,13 @@ void check_loss_args(const std::vector<Tensor>& preds, const Tensor& gt, const T
   check_valid(valid, gt, what);
 }
 
-std::tuple<Tensor, Tensor> sequence_loss_impl(const std::vector<Tensor>& preds, const Tensor& gt, const Tensor& valid,
-                                              at::ArrayRef<double> weights, double max_flow, bool run) {
+std::tuple<Tensor, Tensor> sequence_loss(bool run, const std::vector<Tensor>& preds, const Tensor& gt,
+                                         const Tensor& valid, at::ArrayRef<double> weights, double max_flow) {
   const char* what = "sequence_loss";
   check_loss_args(preds, gt, valid, weights, what);
   Tensor loss = at::empty({}, gt.options().dtype(at::kFloat)), stats = at::empty({8}, gt.options().dtype(at::kDouble));
   if (!run) return {loss, stats};
-  TORCH_CHECK(gt.is_cuda(), what, ": flow_gt is on ", gt.device(), kNoCpu);
+  check_on_gpu(gt, "flow_gt", what);
   const int64_t b = gt.size(0), h = gt.size(2), w = gt.size(3), n = (int64_t)preds.size();
   if (b * h * w == 0)  // the mean of no elements
     return {loss.fill_(std::numeric_limits<float>::quiet_NaN()), stats.zero_()};
@@ -767,30 +681,21 @@ std::tuple<Tensor, Tensor> sequence_loss_impl(const std::vector<Tensor>& preds, 
                what);
   return {loss, stats};
 }
-std::tuple<Tensor, Tensor> sequence_loss_hip(const std::vector<Tensor>& p, const Tensor& gt, const Tensor& v,
-                                             at::ArrayRef<double> w, double m) {
-  return sequence_loss_impl(p, gt, v, w, m, true);
-}
-std::tuple<Tensor, Tensor> sequence_loss_meta(const std::vector<Tensor>& p, const Tensor& gt, const Tensor& v,
-                                              at::ArrayRef<double> w, double m) {
-  return sequence_loss_impl(p, gt, v, w, m, false);
-}
 
 // one gradient per prediction; a prediction with need[i] == 0 gets an empty (0-element) tensor and the kernel a null
 // pointer for it (nothing read or written for that prediction)
-std::vector<Tensor> sequence_loss_backward_impl(const Tensor& gout, const std::vector<Tensor>& preds, const Tensor& gt,
-                                                const Tensor& valid, at::ArrayRef<double> weights, double max_flow,
-                                                at::IntArrayRef need, bool run) {
+std::vector<Tensor> sequence_loss_backward(bool run, const Tensor& gout, const std::vector<Tensor>& preds,
+                                           const Tensor& gt, const Tensor& valid, at::ArrayRef<double> weights,
+                                           double max_flow, at::IntArrayRef need) {
   const char* what = "sequence_loss backward";
   check_loss_args(preds, gt, valid, weights, what);
   const int64_t n = (int64_t)preds.size();
   TORCH_CHECK((int64_t)need.size() == n, what, ": ", need.size(), " gradient flags for ", n, " predictions");
   TORCH_CHECK(gout.numel() == 1 && gout.device() == gt.device(), what, ": grad_out must be one element on the flow's device");
-  const auto fopt = gt.options().dtype(at::kFloat);
   std::vector<Tensor> grads;
-  for (int64_t i = 0; i < n; ++i) grads.push_back(need[i] ? at::empty(gt.sizes(), fopt) : at::empty({0}, fopt));
+  for (int64_t i = 0; i < n; ++i) grads.push_back(wanted(need[i] != 0, gt.sizes(), gt.options().dtype(at::kFloat)));
   if (!run) return grads;
-  TORCH_CHECK(gt.is_cuda(), what, ": flow_gt is on ", gt.device(), kNoCpu);
+  check_on_gpu(gt, "flow_gt", what);
   const int64_t b = gt.size(0), h = gt.size(2), w = gt.size(3);
   if (b * h * w == 0) return grads;
   Tensor g32 = gpu_f32(gt, "flow_gt", what), go = gpu_f32(gout, "grad_out", what).reshape({1});
@@ -811,14 +716,6 @@ std::vector<Tensor> sequence_loss_backward_impl(const Tensor& gout, const std::v
                what);
   return grads;
 }
-std::vector<Tensor> sequence_loss_backward_hip(const Tensor& go, const std::vector<Tensor>& p, const Tensor& gt, const Tensor& v,
-                                               at::ArrayRef<double> w, double m, at::IntArrayRef need) {
-  return sequence_loss_backward_impl(go, p, gt, v, w, m, need, true);
-}
-std::vector<Tensor> sequence_loss_backward_meta(const Tensor& go, const std::vector<Tensor>& p, const Tensor& gt, const Tensor& v,
-                                                at::ArrayRef<double> w, double m, at::IntArrayRef need) {
-  return sequence_loss_backward_impl(go, p, gt, v, w, m, need, false);
-}
 
 // ---------------------------------------------------------------- convex upsampling (upsample.hip, upsample_backward.hip)
 void check_upsample(const Tensor& flow, const Tensor& mask, const char* what) {
@@ -830,11 +727,7 @@ void check_upsample(const Tensor& flow, const Tensor& mask, const char* what) {
               " is past the kernel's grid (B, H <= 65535, 8 W < 2^31)");
 }
 
-void check_on_gpu(const Tensor& t, const char* name, const char* what) {
-  TORCH_CHECK(t.is_cuda(), what, ": ", name, " is on ", t.device(), kNoCpu);
-}
-
-Tensor convex_upsample_impl(const Tensor& flow, const Tensor& mask, bool run) {
+Tensor convex_upsample(bool run, const Tensor& flow, const Tensor& mask) {
   const char* what = "upsample_flow";
   if (run) check_on_gpu(flow, "flow", what), check_on_gpu(mask, "mask", what);
   check_upsample(flow, mask, what);
@@ -849,13 +742,11 @@ Tensor convex_upsample_impl(const Tensor& flow, const Tensor& mask, bool run) {
                what);
   return out;
 }
-Tensor convex_upsample_hip(const Tensor& flow, const Tensor& mask) { return convex_upsample_impl(flow, mask, true); }
-Tensor convex_upsample_meta(const Tensor& flow, const Tensor& mask) { return convex_upsample_impl(flow, mask, false); }
 
 // (grad_flow, grad_mask); an output not wanted is an empty (0-element) tensor and the kernel gets a null pointer for it
 // (no grad_mask stores / no flow phase). The (B, 18, H, W) tap-sum scratch of the flow gradient is allocated here.
-std::tuple<Tensor, Tensor> convex_upsample_backward_impl(const Tensor& gout, const Tensor& flow, const Tensor& mask,
-                                                         std::array<bool, 2> om, bool run) {
+std::tuple<Tensor, Tensor> convex_upsample_backward(bool run, const Tensor& gout, const Tensor& flow, const Tensor& mask,
+                                                    std::array<bool, 2> om) {
   const char* what = "upsample_flow backward";
   if (run) check_on_gpu(gout, "grad_out", what), check_on_gpu(flow, "flow", what), check_on_gpu(mask, "mask", what);
   check_upsample(flow, mask, what);
@@ -864,8 +755,7 @@ std::tuple<Tensor, Tensor> convex_upsample_backward_impl(const Tensor& gout, con
               what, ": grad_out ", gout.sizes(), " must be (B, 2, 8H, 8W) of flow ", flow.sizes());
   TORCH_CHECK(gout.device() == flow.device(), what, ": grad_out and flow are on different devices");
   const auto fopt = flow.options().dtype(at::kFloat), mopt = mask.options().dtype(at::kFloat);
-  if (!run)
-    return {at::empty(om[0] ? flow.sizes() : at::IntArrayRef{0}, fopt), at::empty(om[1] ? mask.sizes() : at::IntArrayRef{0}, mopt)};
+  if (!run) return {wanted(om[0], flow.sizes(), fopt), wanted(om[1], mask.sizes(), mopt)};
   Tensor go = gpu_f32(gout, "grad_out", what), fl = gpu_f32(flow, "flow", what), mk = gpu_f32(mask, "mask", what);
   Tensor gf = om[0] ? at::empty_like(fl) : at::empty({0}, fopt), gm = om[1] ? at::empty_like(mk) : at::empty({0}, mopt);
   if (fl.numel() == 0 || (!om[0] && !om[1])) return {gf, gm};
@@ -878,18 +768,23 @@ std::tuple<Tensor, Tensor> convex_upsample_backward_impl(const Tensor& gout, con
                what);
   return {gf, gm};
 }
-std::tuple<Tensor, Tensor> convex_upsample_backward_hip(const Tensor& go, const Tensor& fl, const Tensor& mk,
-                                                        std::array<bool, 2> om) {
-  return convex_upsample_backward_impl(go, fl, mk, om, true);
-}
-std::tuple<Tensor, Tensor> convex_upsample_backward_meta(const Tensor& go, const Tensor& fl, const Tensor& mk,
-                                                         std::array<bool, 2> om) {
-  return convex_upsample_backward_impl(go, fl, mk, om, false);
+
+// (grad_x, grad_weight, grad_bias) of the conv and norm layers: an output not wanted is an empty (0-element) tensor and
+// is not formed. With no pixels the parameter gradients are empty sums:
+Tensor3 zero_param_grads(Tensor gx, Tensor gw, Tensor gb, std::array<bool, 3> om) {
+  if (om[1]) gw.zero_();
+  if (om[2]) gb.zero_();
+  return Tensor3(gx, gw, gb);
 }
 
-// ---------------------------------------------------------------- update-block convolutions under autograd (conv_backward.hip)
-// The geometry the native backward covers: stride 1, dilation 1, groups 1, odd kernel <= 7, zero padding (kh/2, kw/2).
-void check_conv_same(const Tensor& x, const Tensor& weight, const char* what) {
+// ---------------------------------------------------------------- convolutions under autograd (conv_backward.hip)
+// conv2d_same (the update block's layers: stride 1) and conv2d_strided (the encoders': stride 1 or 2) are one forward
+// and one backward. The geometry the native backward covers: dilation 1, groups 1, odd kernel <= 7, zero padding
+// (kh/2, kw/2); the output is ((H + s - 1) / s, (W + s - 1) / s). No stride means conv2d_same: its own messages and the
+// stride-1 entry points of conv_backward.hip, which differ from the strided ones at stride 1 in the summation order of
+// the weight gradient (those fold (channel, tap) for a small Cin).
+using Stride = c10::optional<int64_t>;
+void check_conv(const Tensor& x, const Tensor& weight, Stride stride, const char* what) {
   TORCH_CHECK(x.dim() == 4 && weight.dim() == 4 && weight.size(1) == x.size(1), what, ": x ", x.sizes(),
               " must be (B, Cin, H, W) and weight ", weight.sizes(), " (Cout, Cin, kh, kw) (groups = 1)");
   const int64_t kh = weight.size(2), kw = weight.size(3);
@@ -899,82 +794,14 @@ void check_conv_same(const Tensor& x, const Tensor& weight, const char* what) {
               x.scalar_type(), " and ", weight.scalar_type());
   TORCH_CHECK(x.device() == weight.device(), what, ": x and weight are on different devices");
   TORCH_CHECK(weight.size(0) >= 1 && weight.size(1) >= 1, what, ": weight ", weight.sizes(), " has no channels");
+  if (stride) TORCH_CHECK(*stride == 1 || *stride == 2, what, ": stride ", *stride, " is not supported (1 or 2, the same in y and x)");
 }
 
-Tensor conv2d_same_impl(const Tensor& x, const Tensor& weight, const c10::optional<Tensor>& bias, bool run) {
-  const char* what = "conv2d_same";
+Tensor conv2d_forward(bool run, const Tensor& x, const Tensor& weight, const c10::optional<Tensor>& bias, Stride strided) {
+  const char* what = strided ? "conv2d_strided" : "conv2d_same";
   if (run) check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
-  check_conv_same(x, weight, what);
-  if (bias.has_value())
-    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == weight.size(0) && bias->scalar_type() == at::kFloat &&
-                    bias->device() == x.device(),
-                what, ": bias must be float32 (Cout) on x's device, got ", bias->scalar_type(), " ", bias->sizes());
-  if (!run) return at::empty({x.size(0), weight.size(0), x.size(2), x.size(3)}, x.options());
-  // the forward is the nn.Conv2d's own call (ATen / MIOpen): the same bits; only the backward is replaced
-  return at::conv2d(x, weight, bias, {1, 1}, {weight.size(2) / 2, weight.size(3) / 2}, {1, 1}, 1);
-}
-Tensor conv2d_same_hip(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b) { return conv2d_same_impl(x, w, b, true); }
-Tensor conv2d_same_meta(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b) { return conv2d_same_impl(x, w, b, false); }
-
-// (grad_x, grad_weight, grad_bias); an output not wanted is an empty (0-element) tensor and is not formed. The K-slab
-// workspace of the weight / bias gradient is allocated here (uninitialised: the kernels write all of it they read).
-using Tensor3 = std::tuple<Tensor, Tensor, Tensor>;
-Tensor3 conv2d_same_backward_impl(const Tensor& gout, const Tensor& x, const Tensor& weight, std::array<bool, 3> om, bool run) {
-  const char* what = "conv2d_same backward";
-  if (run) check_on_gpu(gout, "grad_out", what), check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
-  check_conv_same(x, weight, what);
-  const int64_t b = x.size(0), cin = x.size(1), h = x.size(2), w = x.size(3);
-  const int64_t cout = weight.size(0), kh = weight.size(2), kw = weight.size(3);
-  TORCH_CHECK(gout.dim() == 4 && gout.size(0) == b && gout.size(1) == cout && gout.size(2) == h && gout.size(3) == w &&
-                  gout.scalar_type() == at::kFloat,
-              what, ": grad_out ", gout.sizes(), " must be float32 (B, Cout, H, W) = (", b, ", ", cout, ", ", h, ", ", w, ")");
-  TORCH_CHECK(gout.device() == x.device(), what, ": grad_out and x are on different devices");
-  const auto opt = x.options();
-  Tensor gx = at::empty(om[0] ? x.sizes() : at::IntArrayRef{0}, opt);
-  Tensor gw = at::empty(om[1] ? weight.sizes() : at::IntArrayRef{0}, opt);
-  Tensor gb = om[2] ? at::empty({cout}, opt) : at::empty({0}, opt);
-  if (!run || !(om[0] || om[1] || om[2])) return Tensor3(gx, gw, gb);
-  if (x.numel() == 0) {  // no pixels: the parameter gradients are empty sums
-    if (om[1]) gw.zero_();
-    if (om[2]) gb.zero_();
-    return Tensor3(gx, gw, gb);
-  }
-  TORCH_CHECK(b <= INT_MAX && h <= INT_MAX && w <= INT_MAX && cout <= INT_MAX && cin <= INT_MAX, what, ": x ", x.sizes(),
-              " is past the kernels' index range");
-  Tensor go = gout.contiguous(), xc = x.contiguous(), wc = weight.contiguous();
-  c10::hip::HIPGuardMasqueradingAsCUDA g(xc.device());
-  if (om[0])
-    check_status(oflow_conv2d_backward_input_f32(go.data_ptr<float>(), wc.data_ptr<float>(), (int)b, (int)cout, (int)cin,
-                                                 (int)h, (int)w, (int)kh, (int)kw, gx.data_ptr<float>(), cur_stream()),
-                 what);
-  if (om[1] || om[2]) {
-    const long long n = oflow_conv2d_backward_weight_workspace_floats((int)b, (int)cout, (int)cin, (int)h, (int)w, (int)kh, (int)kw);
-    Tensor ws = at::empty({(int64_t)n}, opt);
-    check_status(oflow_conv2d_backward_weight_f32(go.data_ptr<float>(), xc.data_ptr<float>(), (int)b, (int)cout, (int)cin,
-                                                  (int)h, (int)w, (int)kh, (int)kw, om[1] ? gw.data_ptr<float>() : nullptr,
-                                                  om[2] ? gb.data_ptr<float>() : nullptr, ws.data_ptr<float>(), cur_stream()),
-                 what);
-  }
-  return Tensor3(gx, gw, gb);
-}
-Tensor3 conv2d_same_backward_hip(const Tensor& go, const Tensor& x, const Tensor& w, std::array<bool, 3> om) {
-  return conv2d_same_backward_impl(go, x, w, om, true);
-}
-Tensor3 conv2d_same_backward_meta(const Tensor& go, const Tensor& x, const Tensor& w, std::array<bool, 3> om) {
-  return conv2d_same_backward_impl(go, x, w, om, false);
-}
-
-// ---------------------------------------------------------------- encoder convolutions under autograd (conv_backward.hip)
-// conv2d_same's geometry with stride 1 or 2: the output is ((H + s - 1) / s, (W + s - 1) / s).
-void check_conv_strided(const Tensor& x, const Tensor& weight, int64_t stride, const char* what) {
-  check_conv_same(x, weight, what);
-  TORCH_CHECK(stride == 1 || stride == 2, what, ": stride ", stride, " is not supported (1 or 2, the same in y and x)");
-}
-
-Tensor conv2d_strided_impl(const Tensor& x, const Tensor& weight, const c10::optional<Tensor>& bias, int64_t stride, bool run) {
-  const char* what = "conv2d_strided";
-  if (run) check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
-  check_conv_strided(x, weight, stride, what);
+  check_conv(x, weight, strided, what);
+  const int64_t stride = strided.value_or(1);
   if (bias.has_value())
     TORCH_CHECK(bias->dim() == 1 && bias->size(0) == weight.size(0) && bias->scalar_type() == at::kFloat &&
                     bias->device() == x.device(),
@@ -985,62 +812,65 @@ Tensor conv2d_strided_impl(const Tensor& x, const Tensor& weight, const c10::opt
   // the forward is the nn.Conv2d's own call (ATen / MIOpen): the same bits; only the backward is replaced
   return at::conv2d(x, weight, bias, {stride, stride}, {weight.size(2) / 2, weight.size(3) / 2}, {1, 1}, 1);
 }
-Tensor conv2d_strided_hip(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t s) {
-  return conv2d_strided_impl(x, w, b, s, true);
-}
-Tensor conv2d_strided_meta(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t s) {
-  return conv2d_strided_impl(x, w, b, s, false);
-}
 
-Tensor3 conv2d_strided_backward_impl(const Tensor& gout, const Tensor& x, const Tensor& weight, int64_t stride,
-                                     std::array<bool, 3> om, bool run) {
-  const char* what = "conv2d_strided backward";
+// The K-slab workspace of the weight / bias gradient is allocated here (uninitialised: the kernels write all of it they
+// read).
+Tensor3 conv2d_backward(bool run, const Tensor& gout, const Tensor& x, const Tensor& weight, Stride strided,
+                        std::array<bool, 3> om) {
+  const char* what = strided ? "conv2d_strided backward" : "conv2d_same backward";
   if (run) check_on_gpu(gout, "grad_out", what), check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
-  check_conv_strided(x, weight, stride, what);
+  check_conv(x, weight, strided, what);
+  const int64_t stride = strided.value_or(1);
   const int64_t b = x.size(0), cin = x.size(1), h = x.size(2), w = x.size(3);
   const int64_t cout = weight.size(0), kh = weight.size(2), kw = weight.size(3);
   const int64_t ho = (h + stride - 1) / stride, wo = (w + stride - 1) / stride;
   TORCH_CHECK(gout.dim() == 4 && gout.size(0) == b && gout.size(1) == cout && gout.size(2) == ho && gout.size(3) == wo &&
                   gout.scalar_type() == at::kFloat,
-              what, ": grad_out ", gout.sizes(), " must be float32 (B, Cout, H', W') = (", b, ", ", cout, ", ", ho, ", ", wo, ")");
+              what, ": grad_out ", gout.sizes(), " must be float32 (B, Cout, ", strided ? "H', W'" : "H, W", ") = (", b, ", ",
+              cout, ", ", ho, ", ", wo, ")");
   TORCH_CHECK(gout.device() == x.device(), what, ": grad_out and x are on different devices");
   const auto opt = x.options();
-  Tensor gx = at::empty(om[0] ? x.sizes() : at::IntArrayRef{0}, opt);
-  Tensor gw = at::empty(om[1] ? weight.sizes() : at::IntArrayRef{0}, opt);
-  Tensor gb = om[2] ? at::empty({cout}, opt) : at::empty({0}, opt);
+  Tensor gx = wanted(om[0], x.sizes(), opt), gw = wanted(om[1], weight.sizes(), opt), gb = wanted(om[2], {cout}, opt);
   if (!run || !(om[0] || om[1] || om[2])) return Tensor3(gx, gw, gb);
-  if (x.numel() == 0) {  // no pixels: the parameter gradients are empty sums
-    if (om[1]) gw.zero_();
-    if (om[2]) gb.zero_();
-    return Tensor3(gx, gw, gb);
-  }
+  if (x.numel() == 0) return zero_param_grads(gx, gw, gb, om);
   TORCH_CHECK(b <= INT_MAX && h <= INT_MAX && w <= INT_MAX && cout <= INT_MAX && cin <= INT_MAX, what, ": x ", x.sizes(),
               " is past the kernels' index range");
   Tensor go = gout.contiguous(), xc = x.contiguous(), wc = weight.contiguous();
   c10::hip::HIPGuardMasqueradingAsCUDA g(xc.device());
+  const int B = (int)b, Co = (int)cout, Ci = (int)cin, H = (int)h, W = (int)w, KH = (int)kh, KW = (int)kw, S = (int)stride;
   if (om[0])
-    check_status(oflow_conv2d_strided_backward_input_f32(go.data_ptr<float>(), wc.data_ptr<float>(), (int)b, (int)cout,
-                                                         (int)cin, (int)h, (int)w, (int)kh, (int)kw, (int)stride,
-                                                         gx.data_ptr<float>(), cur_stream()),
+    check_status(strided ? oflow_conv2d_strided_backward_input_f32(go.data_ptr<float>(), wc.data_ptr<float>(), B, Co, Ci, H,
+                                                                   W, KH, KW, S, gx.data_ptr<float>(), cur_stream())
+                         : oflow_conv2d_backward_input_f32(go.data_ptr<float>(), wc.data_ptr<float>(), B, Co, Ci, H, W, KH,
+                                                           KW, gx.data_ptr<float>(), cur_stream()),
                  what);
   if (om[1] || om[2]) {
-    const long long n = oflow_conv2d_strided_backward_weight_workspace_floats((int)b, (int)cout, (int)cin, (int)h, (int)w,
-                                                                              (int)kh, (int)kw, (int)stride);
+    const long long n = strided ? oflow_conv2d_strided_backward_weight_workspace_floats(B, Co, Ci, H, W, KH, KW, S)
+                                : oflow_conv2d_backward_weight_workspace_floats(B, Co, Ci, H, W, KH, KW);
     Tensor ws = at::empty({(int64_t)n}, opt);
-    check_status(oflow_conv2d_strided_backward_weight_f32(go.data_ptr<float>(), xc.data_ptr<float>(), (int)b, (int)cout,
-                                                          (int)cin, (int)h, (int)w, (int)kh, (int)kw, (int)stride,
-                                                          om[1] ? gw.data_ptr<float>() : nullptr,
-                                                          om[2] ? gb.data_ptr<float>() : nullptr, ws.data_ptr<float>(),
-                                                          cur_stream()),
+    float* pgw = om[1] ? gw.data_ptr<float>() : nullptr;
+    float* pgb = om[2] ? gb.data_ptr<float>() : nullptr;
+    check_status(strided ? oflow_conv2d_strided_backward_weight_f32(go.data_ptr<float>(), xc.data_ptr<float>(), B, Co, Ci, H,
+                                                                    W, KH, KW, S, pgw, pgb, ws.data_ptr<float>(), cur_stream())
+                         : oflow_conv2d_backward_weight_f32(go.data_ptr<float>(), xc.data_ptr<float>(), B, Co, Ci, H, W, KH,
+                                                            KW, pgw, pgb, ws.data_ptr<float>(), cur_stream()),
                  what);
   }
   return Tensor3(gx, gw, gb);
 }
-Tensor3 conv2d_strided_backward_hip(const Tensor& go, const Tensor& x, const Tensor& w, int64_t s, std::array<bool, 3> om) {
-  return conv2d_strided_backward_impl(go, x, w, s, om, true);
+
+Tensor conv2d_same(bool run, const Tensor& x, const Tensor& weight, const c10::optional<Tensor>& bias) {
+  return conv2d_forward(run, x, weight, bias, c10::nullopt);
 }
-Tensor3 conv2d_strided_backward_meta(const Tensor& go, const Tensor& x, const Tensor& w, int64_t s, std::array<bool, 3> om) {
-  return conv2d_strided_backward_impl(go, x, w, s, om, false);
+Tensor conv2d_strided(bool run, const Tensor& x, const Tensor& weight, const c10::optional<Tensor>& bias, int64_t stride) {
+  return conv2d_forward(run, x, weight, bias, stride);
+}
+Tensor3 conv2d_same_backward(bool run, const Tensor& gout, const Tensor& x, const Tensor& weight, std::array<bool, 3> om) {
+  return conv2d_backward(run, gout, x, weight, c10::nullopt, om);
+}
+Tensor3 conv2d_strided_backward(bool run, const Tensor& gout, const Tensor& x, const Tensor& weight, int64_t stride,
+                                std::array<bool, 3> om) {
+  return conv2d_backward(run, gout, x, weight, stride, om);
 }
 
 // ---------------------------------------------------------------- encoder norm layers under autograd (norm_backward.hip)
@@ -1057,8 +887,18 @@ void check_norm_grad(const Tensor& gout, const Tensor& x, const char* what) {
               " is past the kernels' index range");
 }
 
+// the per-channel vectors of a batch norm, each float32 (C) on x's device
+using NamedTensors = std::initializer_list<std::pair<const char*, const Tensor*>>;
+void check_channel_vectors(const Tensor& x, NamedTensors params, const char* what) {
+  for (auto& p : params)
+    TORCH_CHECK(p.second->dim() == 1 && p.second->size(0) == x.size(1) && p.second->scalar_type() == at::kFloat &&
+                    p.second->device() == x.device(),
+                what, ": ", p.first, " must be float32 (C) on x's device, got ", p.second->scalar_type(), " ",
+                p.second->sizes());
+}
+
 // relu(instance_norm(x)) / instance_norm(x) of an nn.InstanceNorm2d without affine parameters or running statistics
-Tensor instance_norm_act_impl(const Tensor& x, double eps, bool relu, bool run) {
+Tensor instance_norm_act(bool run, const Tensor& x, double eps, bool relu) {
   const char* what = "instance_norm_act";
   if (run) check_on_gpu(x, "x", what);
   check_norm_input(x, what);
@@ -1067,10 +907,8 @@ Tensor instance_norm_act_impl(const Tensor& x, double eps, bool relu, bool run) 
   Tensor y = at::instance_norm(x, {}, {}, {}, {}, true, 0.1, eps, at::globalContext().userEnabledCuDNN());
   return relu ? at::relu_(y) : y;
 }
-Tensor instance_norm_act_hip(const Tensor& x, double eps, bool relu) { return instance_norm_act_impl(x, eps, relu, true); }
-Tensor instance_norm_act_meta(const Tensor& x, double eps, bool relu) { return instance_norm_act_impl(x, eps, relu, false); }
 
-Tensor instance_norm_act_backward_impl(const Tensor& gout, const Tensor& x, double eps, bool relu, bool run) {
+Tensor instance_norm_act_backward(bool run, const Tensor& gout, const Tensor& x, double eps, bool relu) {
   const char* what = "instance_norm_act backward";
   if (run) check_on_gpu(gout, "grad_out", what), check_on_gpu(x, "x", what);
   check_norm_input(x, what);
@@ -1085,64 +923,33 @@ Tensor instance_norm_act_backward_impl(const Tensor& gout, const Tensor& x, doub
                what);
   return gx;
 }
-Tensor instance_norm_act_backward_hip(const Tensor& go, const Tensor& x, double eps, bool relu) {
-  return instance_norm_act_backward_impl(go, x, eps, relu, true);
-}
-Tensor instance_norm_act_backward_meta(const Tensor& go, const Tensor& x, double eps, bool relu) {
-  return instance_norm_act_backward_impl(go, x, eps, relu, false);
-}
-
-void check_bn_params(const Tensor& x, const Tensor& weight, const Tensor& bias, const Tensor& rm, const Tensor& rv,
-                     const char* what) {
-  const char* names[4] = {"weight", "bias", "running_mean", "running_var"};
-  const Tensor* ts[4] = {&weight, &bias, &rm, &rv};
-  for (int i = 0; i < 4; ++i)
-    TORCH_CHECK(ts[i]->dim() == 1 && ts[i]->size(0) == x.size(1) && ts[i]->scalar_type() == at::kFloat &&
-                    ts[i]->device() == x.device(),
-                what, ": ", names[i], " must be float32 (C) on x's device, got ", ts[i]->scalar_type(), " ", ts[i]->sizes());
-}
 
 // relu(batch_norm(x)) / batch_norm(x) of an nn.BatchNorm2d on its running statistics (eval mode)
-Tensor frozen_batch_norm_act_impl(const Tensor& x, const Tensor& weight, const Tensor& bias, const Tensor& rm,
-                                  const Tensor& rv, double eps, bool relu, bool run) {
+Tensor frozen_batch_norm_act(bool run, const Tensor& x, const Tensor& weight, const Tensor& bias, const Tensor& rm,
+                             const Tensor& rv, double eps, bool relu) {
   const char* what = "frozen_batch_norm_act";
   if (run) check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
   check_norm_input(x, what);
-  check_bn_params(x, weight, bias, rm, rv, what);
+  check_channel_vectors(x, {{"weight", &weight}, {"bias", &bias}, {"running_mean", &rm}, {"running_var", &rv}}, what);
   if (!run) return at::empty(x.sizes(), x.options());
   // the module's own ATen call (F.batch_norm, training = False) and nn.ReLU's: the same bits
   Tensor y = at::batch_norm(x, weight, bias, rm, rv, false, 0.1, eps, at::globalContext().userEnabledCuDNN());
   return relu ? at::relu_(y) : y;
 }
-Tensor frozen_batch_norm_act_hip(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& rm, const Tensor& rv,
-                                 double eps, bool relu) {
-  return frozen_batch_norm_act_impl(x, w, b, rm, rv, eps, relu, true);
-}
-Tensor frozen_batch_norm_act_meta(const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& rm, const Tensor& rv,
-                                  double eps, bool relu) {
-  return frozen_batch_norm_act_impl(x, w, b, rm, rv, eps, relu, false);
-}
 
-// (grad_x, grad_weight, grad_bias); an output not wanted is an empty (0-element) tensor and is not formed
-Tensor3 frozen_batch_norm_act_backward_impl(const Tensor& gout, const Tensor& x, const Tensor& weight, const Tensor& bias,
-                                            const Tensor& rm, const Tensor& rv, double eps, bool relu,
-                                            std::array<bool, 3> om, bool run) {
+Tensor3 frozen_batch_norm_act_backward(bool run, const Tensor& gout, const Tensor& x, const Tensor& weight,
+                                       const Tensor& bias, const Tensor& rm, const Tensor& rv, double eps, bool relu,
+                                       std::array<bool, 3> om) {
   const char* what = "frozen_batch_norm_act backward";
   if (run) check_on_gpu(gout, "grad_out", what), check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
   check_norm_input(x, what);
-  check_bn_params(x, weight, bias, rm, rv, what);
+  check_channel_vectors(x, {{"weight", &weight}, {"bias", &bias}, {"running_mean", &rm}, {"running_var", &rv}}, what);
   check_norm_grad(gout, x, what);
   const int64_t b = x.size(0), c = x.size(1), hw = x.size(2) * x.size(3);
   const auto opt = x.options();
-  Tensor gx = at::empty(om[0] ? x.sizes() : at::IntArrayRef{0}, opt);
-  Tensor gw = om[1] ? at::empty({c}, opt) : at::empty({0}, opt);
-  Tensor gb = om[2] ? at::empty({c}, opt) : at::empty({0}, opt);
+  Tensor gx = wanted(om[0], x.sizes(), opt), gw = wanted(om[1], {c}, opt), gb = wanted(om[2], {c}, opt);
   if (!run || !(om[0] || om[1] || om[2])) return Tensor3(gx, gw, gb);
-  if (x.numel() == 0) {  // no pixels: the parameter gradients are empty sums
-    if (om[1]) gw.zero_();
-    if (om[2]) gb.zero_();
-    return Tensor3(gx, gw, gb);
-  }
+  if (x.numel() == 0) return zero_param_grads(gx, gw, gb, om);
   Tensor go = gout.contiguous(), xc = x.contiguous();
   Tensor wc = weight.contiguous(), bc = bias.contiguous(), rmc = rm.contiguous(), rvc = rv.contiguous();
   c10::hip::HIPGuardMasqueradingAsCUDA g(xc.device());
@@ -1156,38 +963,21 @@ Tensor3 frozen_batch_norm_act_backward_impl(const Tensor& gout, const Tensor& x,
                what);
   return Tensor3(gx, gw, gb);
 }
-Tensor3 frozen_batch_norm_act_backward_hip(const Tensor& go, const Tensor& x, const Tensor& w, const Tensor& b,
-                                           const Tensor& rm, const Tensor& rv, double eps, bool relu,
-                                           std::array<bool, 3> om) {
-  return frozen_batch_norm_act_backward_impl(go, x, w, b, rm, rv, eps, relu, om, true);
-}
-Tensor3 frozen_batch_norm_act_backward_meta(const Tensor& go, const Tensor& x, const Tensor& w, const Tensor& b,
-                                            const Tensor& rm, const Tensor& rv, double eps, bool relu,
-                                            std::array<bool, 3> om) {
-  return frozen_batch_norm_act_backward_impl(go, x, w, b, rm, rv, eps, relu, om, false);
-}
 
 // ---------------------------------------------------------------- batch norm on batch statistics (batch_norm.hip)
-void check_bn_batch(const Tensor& x, const Tensor& weight, const Tensor& bias, const Tensor* mean, const Tensor* var,
-                    const char* what) {
-  const char* names[4] = {"weight", "bias", "mean", "var"};
-  const Tensor* ts[4] = {&weight, &bias, mean, var};
-  for (int i = 0; i < 4; ++i)
-    if (ts[i])
-      TORCH_CHECK(ts[i]->dim() == 1 && ts[i]->size(0) == x.size(1) && ts[i]->scalar_type() == at::kFloat &&
-                      ts[i]->device() == x.device(),
-                  what, ": ", names[i], " must be float32 (C) on x's device, got ", ts[i]->scalar_type(), " ", ts[i]->sizes());
+void check_bn_batch(const Tensor& x, NamedTensors params, const char* what) {
+  check_channel_vectors(x, params, what);
   TORCH_CHECK(x.size(0) <= INT_MAX && x.size(1) <= INT_MAX && x.size(2) * x.size(3) <= INT_MAX, what, ": x ", x.sizes(),
               " is past the kernels' index range");
 }
 
 // relu(batch_norm(x)) / batch_norm(x) of an nn.BatchNorm2d on batch statistics -> (y, mean, biased var); the running
 // statistics are the caller's to update (extractor.py: enc_norm_act)
-Tensor3 batch_norm_act_impl(const Tensor& x, const Tensor& weight, const Tensor& bias, double eps, bool relu, bool run) {
+Tensor3 batch_norm_act(bool run, const Tensor& x, const Tensor& weight, const Tensor& bias, double eps, bool relu) {
   const char* what = "batch_norm_act";
   if (run) check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
   check_norm_input(x, what);
-  check_bn_batch(x, weight, bias, nullptr, nullptr, what);
+  check_bn_batch(x, {{"weight", &weight}, {"bias", &bias}}, what);
   const int64_t b = x.size(0), c = x.size(1), hw = x.size(2) * x.size(3);
   const auto opt = x.options();
   Tensor y = at::empty(x.sizes(), opt), mean = at::empty({c}, opt), var = at::empty({c}, opt);
@@ -1206,33 +996,19 @@ Tensor3 batch_norm_act_impl(const Tensor& x, const Tensor& weight, const Tensor&
                what);
   return Tensor3(y, mean, var);
 }
-Tensor3 batch_norm_act_hip(const Tensor& x, const Tensor& w, const Tensor& b, double eps, bool relu) {
-  return batch_norm_act_impl(x, w, b, eps, relu, true);
-}
-Tensor3 batch_norm_act_meta(const Tensor& x, const Tensor& w, const Tensor& b, double eps, bool relu) {
-  return batch_norm_act_impl(x, w, b, eps, relu, false);
-}
 
-// (grad_x, grad_weight, grad_bias); an output not wanted is an empty (0-element) tensor and is not formed
-Tensor3 batch_norm_act_backward_impl(const Tensor& gout, const Tensor& x, const Tensor& weight, const Tensor& bias,
-                                     const Tensor& mean, const Tensor& var, double eps, bool relu, std::array<bool, 3> om,
-                                     bool run) {
+Tensor3 batch_norm_act_backward(bool run, const Tensor& gout, const Tensor& x, const Tensor& weight, const Tensor& bias,
+                                const Tensor& mean, const Tensor& var, double eps, bool relu, std::array<bool, 3> om) {
   const char* what = "batch_norm_act backward";
   if (run) check_on_gpu(gout, "grad_out", what), check_on_gpu(x, "x", what), check_on_gpu(weight, "weight", what);
   check_norm_input(x, what);
-  check_bn_batch(x, weight, bias, &mean, &var, what);
+  check_bn_batch(x, {{"weight", &weight}, {"bias", &bias}, {"mean", &mean}, {"var", &var}}, what);
   check_norm_grad(gout, x, what);
   const int64_t b = x.size(0), c = x.size(1), hw = x.size(2) * x.size(3);
   const auto opt = x.options();
-  Tensor gx = at::empty(om[0] ? x.sizes() : at::IntArrayRef{0}, opt);
-  Tensor gw = om[1] ? at::empty({c}, opt) : at::empty({0}, opt);
-  Tensor gb = om[2] ? at::empty({c}, opt) : at::empty({0}, opt);
+  Tensor gx = wanted(om[0], x.sizes(), opt), gw = wanted(om[1], {c}, opt), gb = wanted(om[2], {c}, opt);
   if (!run || !(om[0] || om[1] || om[2])) return Tensor3(gx, gw, gb);
-  if (x.numel() == 0) {  // no pixels: the parameter gradients are empty sums
-    if (om[1]) gw.zero_();
-    if (om[2]) gb.zero_();
-    return Tensor3(gx, gw, gb);
-  }
+  if (x.numel() == 0) return zero_param_grads(gx, gw, gb, om);
   Tensor go = gout.contiguous(), xc = x.contiguous();
   Tensor wc = weight.contiguous(), bc = bias.contiguous(), mc = mean.contiguous(), vc = var.contiguous();
   c10::hip::HIPGuardMasqueradingAsCUDA g(xc.device());
@@ -1245,17 +1021,9 @@ Tensor3 batch_norm_act_backward_impl(const Tensor& gout, const Tensor& x, const 
                what);
   return Tensor3(gx, gw, gb);
 }
-Tensor3 batch_norm_act_backward_hip(const Tensor& go, const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& mean,
-                                    const Tensor& var, double eps, bool relu, std::array<bool, 3> om) {
-  return batch_norm_act_backward_impl(go, x, w, b, mean, var, eps, relu, om, true);
-}
-Tensor3 batch_norm_act_backward_meta(const Tensor& go, const Tensor& x, const Tensor& w, const Tensor& b, const Tensor& mean,
-                                     const Tensor& var, double eps, bool relu, std::array<bool, 3> om) {
-  return batch_norm_act_backward_impl(go, x, w, b, mean, var, eps, relu, om, false);
-}
 
 // ---------------------------------------------------------------- warm start (forward_interpolate.hip)
-Tensor forward_interpolate_impl(const Tensor& flow, bool run) {
+Tensor forward_interpolate(bool run, const Tensor& flow) {
   const char* what = "forward_interpolate";
   if (run) check_on_gpu(flow, "flow", what);
   TORCH_CHECK(flow.dim() == 4 && flow.size(1) == 2, what, ": flow must be (B, 2, H, W), got ", flow.sizes());
@@ -1273,14 +1041,10 @@ Tensor forward_interpolate_impl(const Tensor& flow, bool run) {
                what);
   return out;
 }
-Tensor forward_interpolate_hip(const Tensor& flow) { return forward_interpolate_impl(flow, true); }
-Tensor forward_interpolate_meta(const Tensor& flow) { return forward_interpolate_impl(flow, false); }
-
-using Tensor4 = std::tuple<Tensor, Tensor, Tensor, Tensor>;
 
 // ---------------------------------------------------------------- forward-backward consistency (fb_consistency.hip)
-Tensor4 fb_consistency_impl(const Tensor& fw, const Tensor& bw, double alpha, double beta, bool both, bool with_error,
-                            bool run) {
+Tensor4 fb_consistency(bool run, const Tensor& fw, const Tensor& bw, double alpha, double beta, bool both,
+                       bool with_error) {
   const char* what = "fb_consistency";
   if (run) check_on_gpu(fw, "flow_fw", what), check_on_gpu(bw, "flow_bw", what);
   TORCH_CHECK(fw.dim() == 4 && fw.size(1) == 2 && fw.sizes() == bw.sizes(), what, ": flow_fw ", fw.sizes(),
@@ -1305,17 +1069,10 @@ Tensor4 fb_consistency_impl(const Tensor& fw, const Tensor& bw, double alpha, do
                what);
   return Tensor4(m_fw, m_bw, e_fw, e_bw);
 }
-Tensor4 fb_consistency_hip(const Tensor& fw, const Tensor& bw, double alpha, double beta, bool both, bool with_error) {
-  return fb_consistency_impl(fw, bw, alpha, beta, both, with_error, true);
-}
-Tensor4 fb_consistency_meta(const Tensor& fw, const Tensor& bw, double alpha, double beta, bool both, bool with_error) {
-  return fb_consistency_impl(fw, bw, alpha, beta, both, with_error, false);
-}
 
 // ---------------------------------------------------------------- training-batch augmentation (augment.hip)
-Tensor4 augment_batch_impl(const Tensor& img1, const Tensor& img2, const Tensor& flow,
-                           const c10::optional<Tensor>& valid, const Tensor& params, int64_t ch, int64_t cw,
-                           bool run) {
+Tensor4 augment_batch(bool run, const Tensor& img1, const Tensor& img2, const Tensor& flow,
+                      const c10::optional<Tensor>& valid, const Tensor& params, int64_t ch, int64_t cw) {
   const char* what = "augment_batch";
   const bool sparse = valid.has_value();
   if (run) {
@@ -1372,13 +1129,26 @@ Tensor4 augment_batch_impl(const Tensor& img1, const Tensor& img2, const Tensor&
   }
   return Tensor4(o1, o2, of, ov);
 }
-Tensor4 augment_batch_hip(const Tensor& a, const Tensor& b, const Tensor& f, const c10::optional<Tensor>& v,
-                          const Tensor& p, int64_t ch, int64_t cw) {
-  return augment_batch_impl(a, b, f, v, p, ch, cw, true);
-}
-Tensor4 augment_batch_meta(const Tensor& a, const Tensor& b, const Tensor& f, const c10::optional<Tensor>& v,
-                           const Tensor& p, int64_t ch, int64_t cw) {
-  return augment_batch_impl(a, b, f, v, p, ch, cw, false);
+
+// ---------------------------------------------------------------- registration
+// The two kernels the dispatcher gets from one op function R op(bool run, Args...): Args... is deduced from the
+// function pointer (a leading `run` keeps the pack deducible).
+template <auto F>
+struct Kernels;
+template <class R, class... A, R (*F)(bool, A...)>
+struct Kernels<F> {
+  static R launch(A... a) { return F(true, std::forward<A>(a)...); }
+  static R shapes(A... a) { return F(false, std::forward<A>(a)...); }
+};
+
+// One row per op registers its three kernels, so none can be left out of a table. CPU tensors reach the launching
+// kernel, whose first device check raises "no CPU fallback" (there is no CPU path); a missing CPU kernel would turn
+// that into PyTorch's generic "could not run ... with arguments from the 'CPU' backend".
+template <auto F>
+void bind(torch::Library& m, const char* name) {
+  m.impl(name, c10::DispatchKey::CUDA, &Kernels<F>::launch);
+  m.impl(name, c10::DispatchKey::CPU, &Kernels<F>::launch);
+  m.impl(name, c10::DispatchKey::Meta, &Kernels<F>::shapes);
 }
 
 }  // namespace
@@ -1417,113 +1187,38 @@ TORCH_LIBRARY(oflow, m) {
   m.def("forward_interpolate(Tensor flow) -> Tensor");
   m.def("augment_batch(Tensor img1, Tensor img2, Tensor flow, Tensor? valid, Tensor params, int crop_h, int crop_w) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("fb_consistency(Tensor flow_fw, Tensor flow_bw, float alpha, float beta, bool both, bool with_error) -> (Tensor, Tensor, Tensor, Tensor)");
-}
 
-TORCH_LIBRARY_IMPL(oflow, CUDA, m) {
-  m.impl("corr_pyramid", &corr_pyramid_hip);
-  m.impl("corr_pyramid_tiled", &corr_pyramid_tiled_hip);
-  m.impl("corr_lookup", &corr_lookup_hip);
-  m.impl("corr_lookup_tiled", &corr_lookup_tiled_hip);
-  m.impl("corr_lookup_tiled_nhwc", &corr_lookup_tiled_nhwc_hip);
-  m.impl("corr_otf_prepare", &otf_prepare_hip);
-  m.impl("corr_lookup_otf", &corr_lookup_otf_hip);
-  m.impl("corr_lookup_alt", &corr_lookup_alt_hip);
-  m.impl("corr_lookup_alt_backward", &corr_lookup_alt_backward_hip);
-  m.impl("grid_warp", &grid_warp_hip);
-  m.impl("grid_sample", &grid_sample_hip);
-  m.impl("corr_lookup_backward", &lookup_backward_hip);
-  m.impl("corr_pyramid_backward", &pyramid_backward_hip);
-  m.impl("grid_warp_backward", &grid_warp_backward_hip);
-  m.impl("grid_sample_backward", &grid_sample_backward_hip);
-  m.impl("flow_error_stats", &flow_error_stats_hip);
-  m.impl("sequence_loss", &sequence_loss_hip);
-  m.impl("sequence_loss_backward", &sequence_loss_backward_hip);
-  m.impl("convex_upsample", &convex_upsample_hip);
-  m.impl("convex_upsample_backward", &convex_upsample_backward_hip);
-  m.impl("conv2d_same", &conv2d_same_hip);
-  m.impl("conv2d_same_backward", &conv2d_same_backward_hip);
-  m.impl("conv2d_strided", &conv2d_strided_hip);
-  m.impl("conv2d_strided_backward", &conv2d_strided_backward_hip);
-  m.impl("instance_norm_act", &instance_norm_act_hip);
-  m.impl("instance_norm_act_backward", &instance_norm_act_backward_hip);
-  m.impl("frozen_batch_norm_act", &frozen_batch_norm_act_hip);
-  m.impl("frozen_batch_norm_act_backward", &frozen_batch_norm_act_backward_hip);
-  m.impl("batch_norm_act", &batch_norm_act_hip);
-  m.impl("batch_norm_act_backward", &batch_norm_act_backward_hip);
-  m.impl("forward_interpolate", &forward_interpolate_hip);
-  m.impl("augment_batch", &augment_batch_hip);
-  m.impl("fb_consistency", &fb_consistency_hip);
-}
-
-// CPU tensors reach the same kernels, whose first check raises "no CPU fallback" (there is no CPU path)
-TORCH_LIBRARY_IMPL(oflow, CPU, m) {
-  m.impl("corr_pyramid", &corr_pyramid_hip);
-  m.impl("corr_pyramid_tiled", &corr_pyramid_tiled_hip);
-  m.impl("corr_lookup", &corr_lookup_hip);
-  m.impl("corr_lookup_tiled", &corr_lookup_tiled_hip);
-  m.impl("corr_lookup_tiled_nhwc", &corr_lookup_tiled_nhwc_hip);
-  m.impl("corr_otf_prepare", &otf_prepare_hip);
-  m.impl("corr_lookup_otf", &corr_lookup_otf_hip);
-  m.impl("corr_lookup_alt", &corr_lookup_alt_hip);
-  m.impl("corr_lookup_alt_backward", &corr_lookup_alt_backward_hip);
-  m.impl("grid_warp", &grid_warp_hip);
-  m.impl("grid_sample", &grid_sample_hip);
-  m.impl("corr_lookup_backward", &lookup_backward_hip);
-  m.impl("corr_pyramid_backward", &pyramid_backward_hip);
-  m.impl("grid_warp_backward", &grid_warp_backward_hip);
-  m.impl("grid_sample_backward", &grid_sample_backward_hip);
-  m.impl("flow_error_stats", &flow_error_stats_hip);
-  m.impl("sequence_loss", &sequence_loss_hip);
-  m.impl("sequence_loss_backward", &sequence_loss_backward_hip);
-  m.impl("convex_upsample", &convex_upsample_hip);
-  m.impl("convex_upsample_backward", &convex_upsample_backward_hip);
-  m.impl("conv2d_same", &conv2d_same_hip);
-  m.impl("conv2d_same_backward", &conv2d_same_backward_hip);
-  m.impl("conv2d_strided", &conv2d_strided_hip);
-  m.impl("conv2d_strided_backward", &conv2d_strided_backward_hip);
-  m.impl("instance_norm_act", &instance_norm_act_hip);
-  m.impl("instance_norm_act_backward", &instance_norm_act_backward_hip);
-  m.impl("frozen_batch_norm_act", &frozen_batch_norm_act_hip);
-  m.impl("frozen_batch_norm_act_backward", &frozen_batch_norm_act_backward_hip);
-  m.impl("batch_norm_act", &batch_norm_act_hip);
-  m.impl("batch_norm_act_backward", &batch_norm_act_backward_hip);
-  m.impl("forward_interpolate", &forward_interpolate_hip);
-  m.impl("augment_batch", &augment_batch_hip);
-  m.impl("fb_consistency", &fb_consistency_hip);
-}
-
-TORCH_LIBRARY_IMPL(oflow, Meta, m) {
-  m.impl("corr_pyramid", &corr_pyramid_meta);
-  m.impl("corr_pyramid_tiled", &corr_pyramid_tiled_meta);
-  m.impl("corr_lookup", &corr_lookup_meta);
-  m.impl("corr_lookup_tiled", &corr_lookup_meta);
-  m.impl("corr_lookup_tiled_nhwc", &corr_lookup_tiled_nhwc_meta);
-  m.impl("corr_otf_prepare", &otf_prepare_meta);
-  m.impl("corr_lookup_otf", &corr_lookup_otf_meta);
-  m.impl("corr_lookup_alt", &corr_lookup_alt_meta);
-  m.impl("corr_lookup_alt_backward", &corr_lookup_alt_backward_meta);
-  m.impl("grid_warp", &grid_warp_meta);
-  m.impl("grid_sample", &grid_sample_meta);
-  m.impl("corr_lookup_backward", &lookup_backward_meta);
-  m.impl("corr_pyramid_backward", &pyramid_backward_meta);
-  m.impl("grid_warp_backward", &grid_warp_backward_meta);
-  m.impl("grid_sample_backward", &grid_sample_backward_meta);
-  m.impl("flow_error_stats", &flow_error_stats_meta);
-  m.impl("sequence_loss", &sequence_loss_meta);
-  m.impl("sequence_loss_backward", &sequence_loss_backward_meta);
-  m.impl("convex_upsample", &convex_upsample_meta);
-  m.impl("convex_upsample_backward", &convex_upsample_backward_meta);
-  m.impl("conv2d_same", &conv2d_same_meta);
-  m.impl("conv2d_same_backward", &conv2d_same_backward_meta);
-  m.impl("conv2d_strided", &conv2d_strided_meta);
-  m.impl("conv2d_strided_backward", &conv2d_strided_backward_meta);
-  m.impl("instance_norm_act", &instance_norm_act_meta);
-  m.impl("instance_norm_act_backward", &instance_norm_act_backward_meta);
-  m.impl("frozen_batch_norm_act", &frozen_batch_norm_act_meta);
-  m.impl("frozen_batch_norm_act_backward", &frozen_batch_norm_act_backward_meta);
-  m.impl("batch_norm_act", &batch_norm_act_meta);
-  m.impl("batch_norm_act_backward", &batch_norm_act_backward_meta);
-  m.impl("forward_interpolate", &forward_interpolate_meta);
-  m.impl("augment_batch", &augment_batch_meta);
-  m.impl("fb_consistency", &fb_consistency_meta);
+  bind<&corr_pyramid>(m, "corr_pyramid");
+  bind<&corr_pyramid_tiled>(m, "corr_pyramid_tiled");
+  bind<&corr_lookup>(m, "corr_lookup");
+  bind<&corr_lookup_tiled>(m, "corr_lookup_tiled");
+  bind<&corr_lookup_tiled_nhwc>(m, "corr_lookup_tiled_nhwc");
+  bind<&corr_otf_prepare>(m, "corr_otf_prepare");
+  bind<&corr_lookup_otf>(m, "corr_lookup_otf");
+  bind<&corr_lookup_alt>(m, "corr_lookup_alt");
+  bind<&corr_lookup_alt_backward>(m, "corr_lookup_alt_backward");
+  bind<&grid_warp>(m, "grid_warp");
+  bind<&grid_sample>(m, "grid_sample");
+  bind<&corr_lookup_backward>(m, "corr_lookup_backward");
+  bind<&corr_pyramid_backward>(m, "corr_pyramid_backward");
+  bind<&grid_warp_backward>(m, "grid_warp_backward");
+  bind<&grid_sample_backward>(m, "grid_sample_backward");
+  bind<&flow_error_stats>(m, "flow_error_stats");
+  bind<&sequence_loss>(m, "sequence_loss");
+  bind<&sequence_loss_backward>(m, "sequence_loss_backward");
+  bind<&convex_upsample>(m, "convex_upsample");
+  bind<&convex_upsample_backward>(m, "convex_upsample_backward");
+  bind<&conv2d_same>(m, "conv2d_same");
+  bind<&conv2d_same_backward>(m, "conv2d_same_backward");
+  bind<&conv2d_strided>(m, "conv2d_strided");
+  bind<&conv2d_strided_backward>(m, "conv2d_strided_backward");
+  bind<&instance_norm_act>(m, "instance_norm_act");
+  bind<&instance_norm_act_backward>(m, "instance_norm_act_backward");
+  bind<&frozen_batch_norm_act>(m, "frozen_batch_norm_act");
+  bind<&frozen_batch_norm_act_backward>(m, "frozen_batch_norm_act_backward");
+  bind<&batch_norm_act>(m, "batch_norm_act");
+  bind<&batch_norm_act_backward>(m, "batch_norm_act_backward");
+  bind<&forward_interpolate>(m, "forward_interpolate");
+  bind<&augment_batch>(m, "augment_batch");
+  bind<&fb_consistency>(m, "fb_consistency");
 }

@@ -31,82 +31,6 @@ E_TINY = -4
 INTERP = {"bilinear": 0, "nearest": 1, "bicubic": 2}
 PADDING = {"zeros": 0, "border": 1, "reflection": 2}
 
-# every symbol include/oflow.h declares (tests check the library exports them all)
-SYMBOLS = (
-    "oflow_abi_version",
-    "oflow_status_string",
-    "oflow_corr_pyramid_dims",
-    "oflow_corr_pyramid_f32",
-    "oflow_corr_lookup_f32",
-    "oflow_corr_tiled_level_floats",
-    "oflow_corr_pyramid_tiled_f32",
-    "oflow_corr_lookup_tiled_f32",
-    "oflow_corr_untile_f32",
-    "oflow_grid_warp_f32",
-    "oflow_grid_sample_f32",
-    "oflow_corr_otf_prepare_f16",
-    "oflow_corr_lookup_otf_f16",
-    "oflow_bias_act_f32",
-    "oflow_gru_reset_f32",
-    "oflow_gru_blend_f32",
-    "oflow_conv_s32",
-    "oflow_pack_s32_f32",
-    "oflow_flow_prep_s32",
-    "oflow_stem_patches_s32",
-    "oflow_norm_stats_finalize",
-    "oflow_norm_apply_s32",
-    "oflow_convex_upsample_f32",
-    "oflow_corr_lookup_tiled_nhwc_f32",
-    "oflow_corr_lookup_backward_f32",
-    "oflow_corr_pyramid_grad_combine_f32",
-    "oflow_flow_stats_f32",
-    "oflow_flow2rgb_f32",
-    "oflow_flow_pack_f32",
-    "oflow_corr_lookup_convc1_s32",
-    "oflow_corr_pyramid_tiled_s32",
-    "oflow_flow_head2_s32",
-    "oflow_flow_head2_tiled_s32",
-    "oflow_normalize_images_f32",
-    "oflow_replicate_pad_f32",
-    "oflow_corr_fmap_grad_f32",
-    "oflow_grid_warp_backward_f32",
-    "oflow_grid_sample_backward_f32",
-    "oflow_set_range_flag",
-    "oflow_range_flag_exchange",
-    "oflow_flow_head_col2im_f32",
-    "oflow_flow_head_finish_f32",
-    "oflow_timing_event_create",
-    "oflow_timing_event_destroy",
-    "oflow_timing_event_record",
-    "oflow_timing_event_elapsed_ms",
-    "oflow_flow_error_stats_f32",
-    "oflow_sequence_loss_f32",
-    "oflow_sequence_loss_backward_f32",
-    "oflow_convex_upsample_backward_f32",
-    "oflow_corr_lookup_otf_backward_f32",
-    "oflow_forward_interpolate_f32",
-    "oflow_augment_stats_u8",
-    "oflow_augment_dense_f32",
-    "oflow_augment_sparse_flow_f32",
-    "oflow_conv2d_backward_input_f32",
-    "oflow_conv2d_backward_weight_slab_pixels",
-    "oflow_conv2d_backward_weight_workspace_floats",
-    "oflow_conv2d_backward_weight_f32",
-    "oflow_conv2d_strided_backward_input_f32",
-    "oflow_conv2d_strided_backward_weight_workspace_floats",
-    "oflow_conv2d_strided_backward_weight_f32",
-    "oflow_conv2d_strided_backward_weight_generic_f32",
-    "oflow_instance_norm_backward_f32",
-    "oflow_frozen_batch_norm_backward_workspace_floats",
-    "oflow_frozen_batch_norm_backward_f32",
-    "oflow_batch_norm_chunk_elements",
-    "oflow_batch_norm_workspace_floats",
-    "oflow_batch_norm_forward_f32",
-    "oflow_batch_norm_backward_f32",
-    "oflow_fb_consistency_f32",
-)
-
-
 class ConvS32Desc(ctypes.Structure):
     """oflow_conv_s32_desc (include/oflow.h), field for field in the header's order (tests/test_native_abi.py compares
     the offsets with a C compiler's). Zero-filled = every optional feature off."""
@@ -124,6 +48,92 @@ class ConvS32Desc(ctypes.Structure):
         ("nhwc_pixel_stride", _I), ("res_activation", _I), ("s2d", _I), ("d_addend", _P), ("addend_pixel_stride", _L),
         ("d_fh_weights", _P), ("d_fh_partial", _P), ("fh_slabs", _I),
     ]
+
+
+def _signatures():
+    """name -> (restype, argtypes) of every function include/oflow.h declares, in the header's parameter order."""
+    P, I, F, L, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong, ctypes.c_double
+    IP, PP, FP = ctypes.POINTER(I), ctypes.POINTER(P), ctypes.POINTER(F)
+    strided_wgrad = (I, [P, P, I, I, I, I, I, I, I, I, P, P, P, P])
+    return {
+        "oflow_abi_version": (I, []),
+        "oflow_status_string": (ctypes.c_char_p, [I]),
+        "oflow_corr_pyramid_dims": (I, [I, I, I, IP, IP]),
+        "oflow_corr_pyramid_f32": (I, [P, P, I, I, I, I, I, PP, P]),
+        "oflow_corr_lookup_f32": (I, [PP, IP, IP, I, P, I, I, I, I, P, P]),
+        "oflow_corr_tiled_level_floats": (L, [I, I]),
+        "oflow_corr_pyramid_tiled_f32": (I, [P, P, I, I, I, I, I, PP, P]),
+        "oflow_corr_lookup_tiled_f32": (I, [PP, IP, IP, I, P, I, I, I, I, P, P]),
+        "oflow_corr_untile_f32": (I, [P, P, L, I, I, P]),
+        "oflow_grid_warp_f32": (I, [P, P, I, I, I, I, I, I, I, P, P]),
+        "oflow_grid_sample_f32": (I, [P, P, I, I, I, I, I, I, I, I, I, P, P]),
+        "oflow_corr_otf_prepare_f16": (I, [P, P, I, I, I, I, I, P, PP, P, P]),
+        "oflow_corr_lookup_otf_f16": (I, [P, PP, IP, IP, I, P, I, I, I, I, I, P, P]),
+        "oflow_bias_act_f32": (I, [P, L, P, P, L, P, L, I, I, I, I, F, P]),
+        "oflow_gru_reset_f32": (I, [P, L, P, P, L, P, L, I, I, I, P]),
+        "oflow_gru_blend_f32": (I, [P, L, P, P, L, P, P, L, I, I, I, P]),
+        "oflow_conv_s32": (I, [ctypes.POINTER(ConvS32Desc), P]),
+        "oflow_pack_s32_f32": (I, [P, L, I, I, I, I, I, I, P, L, P, L, P, I, P]),
+        "oflow_flow_prep_s32": (I, [P, I, I, I, P, P, L, P, L, P]),
+        "oflow_stem_patches_s32": (I, [P, I, I, I, I, P, I, P]),
+        "oflow_norm_stats_finalize": (I, [P, I, I, I, I, D, P, P, P]),
+        "oflow_norm_apply_s32": (I, [P, I, I, I, I, P, P, I, I, P, L, P, P, P, I, I, P, L, P]),
+        "oflow_convex_upsample_f32": (I, [P, P, I, I, I, P, P]),
+        "oflow_corr_lookup_tiled_nhwc_f32": (I, [PP, IP, IP, I, P, I, I, I, I, P, I, P]),
+        "oflow_corr_lookup_backward_f32": (I, [P, P, I, I, I, I, PP, IP, IP, I, P]),
+        "oflow_corr_pyramid_grad_combine_f32": (I, [PP, IP, IP, I, L, P]),
+        "oflow_flow_stats_f32": (I, [P, I, I, I, I, F, F, I, P, P]),
+        "oflow_flow2rgb_f32": (I, [P, I, I, I, I, I, F, F, I, I, F, P, P, P]),
+        "oflow_flow_pack_f32": (I, [P, I, I, I, I, I, P, P]),
+        "oflow_corr_lookup_convc1_s32": (I, [PP, IP, IP, I, P, I, I, I, I, P, P, P, P, L, P]),
+        "oflow_corr_pyramid_tiled_s32": (I, [P, P, I, I, I, I, I, PP, P]),
+        "oflow_flow_head2_s32": (I, [P, L, I, P, P, I, I, I, P, P]),
+        "oflow_flow_head2_tiled_s32": (I, [P, L, I, P, P, I, I, I, P, P]),
+        "oflow_normalize_images_f32": (I, [P, P, L, P, P, P]),
+        "oflow_replicate_pad_f32": (I, [P, P, I, L, I, I, I, I, I, I, P]),
+        "oflow_corr_fmap_grad_f32": (I, [P, P, P, I, I, I, F, P, P, P]),
+        "oflow_grid_warp_backward_f32": (I, [P, P, P, I, I, I, I, I, I, I, P, P, P]),
+        "oflow_grid_sample_backward_f32": (I, [P, P, P, I, I, I, I, I, I, I, I, I, P, P, P]),
+        "oflow_set_range_flag": (I, [P]),
+        "oflow_range_flag_exchange": (I, [P, P, P]),
+        "oflow_flow_head_col2im_f32": (I, [P, P, I, I, I, P, P]),
+        "oflow_flow_head_finish_f32": (I, [P, I, P, I, I, I, P, P, L, P, L, P]),
+        "oflow_timing_event_create": (I, [PP]),
+        "oflow_timing_event_destroy": (I, [P]),
+        "oflow_timing_event_record": (I, [P, P, I]),
+        "oflow_timing_event_elapsed_ms": (I, [P, P, FP]),
+        "oflow_flow_error_stats_f32": (I, [P, L, L, L, P, L, L, L, P, I, L, L, I, I, I, F, F, F, P, P, P, P]),
+        "oflow_sequence_loss_f32": (I, [PP, I, FP, P, P, I, I, I, I, F, P, P, P, P]),
+        "oflow_sequence_loss_backward_f32": (I, [P, PP, PP, I, FP, P, P, I, I, I, I, F, P]),
+        "oflow_convex_upsample_backward_f32": (I, [P, P, P, I, I, I, P, P, P, P]),
+        "oflow_corr_lookup_otf_backward_f32": (I, [P, P, PP, IP, IP, I, P, I, I, I, I, I, P, P, P, P]),
+        "oflow_forward_interpolate_f32": (I, [P, I, I, I, P, P]),
+        "oflow_augment_stats_u8": (I, [P, P, P, I, I, I, I, P, P]),
+        "oflow_augment_dense_f32": (I, [P, P, P, P, P, I, I, I, I, I, P, P, P, P, P]),
+        "oflow_augment_sparse_flow_f32": (I, [P, P, P, I, I, I, I, I, P, P, P]),
+        "oflow_conv2d_backward_input_f32": (I, [P, P, I, I, I, I, I, I, I, P, P]),
+        "oflow_conv2d_backward_weight_slab_pixels": (I, []),
+        "oflow_conv2d_backward_weight_workspace_floats": (L, [I, I, I, I, I, I, I]),
+        "oflow_conv2d_backward_weight_f32": (I, [P, P, I, I, I, I, I, I, I, P, P, P, P]),
+        "oflow_conv2d_strided_backward_input_f32": (I, [P, P, I, I, I, I, I, I, I, I, P, P]),
+        "oflow_conv2d_strided_backward_weight_workspace_floats": (L, [I, I, I, I, I, I, I, I]),
+        "oflow_conv2d_strided_backward_weight_f32": strided_wgrad,
+        "oflow_conv2d_strided_backward_weight_generic_f32": strided_wgrad,
+        "oflow_instance_norm_backward_f32": (I, [P, P, I, I, D, I, P, P]),
+        "oflow_frozen_batch_norm_backward_workspace_floats": (L, [I, I, I]),
+        "oflow_frozen_batch_norm_backward_f32": (I, [P, P, P, P, P, P, I, I, I, D, I, P, P, P, P, P]),
+        "oflow_batch_norm_chunk_elements": (I, []),
+        "oflow_batch_norm_workspace_floats": (L, [I, I, I]),
+        "oflow_batch_norm_forward_f32": (I, [P, P, P, I, I, I, D, I, P, P, P, P, P]),
+        "oflow_batch_norm_backward_f32": (I, [P, P, P, P, P, P, I, I, I, D, I, P, P, P, P, P]),
+        "oflow_fb_consistency_f32": (I, [P, P, I, I, I, F, F, P, P, P, P, P]),
+    }
+
+
+_SIGNATURES = _signatures()
+# every symbol include/oflow.h declares (tests check the library exports them all): a symbol cannot be listed here
+# without a signature
+SYMBOLS = tuple(_SIGNATURES)
 
 
 _lib = None
@@ -227,146 +237,9 @@ def load() -> ctypes.CDLL:
             "(or __graft_entry__.build()); the MI355X path has no CPU fallback"
         )
     lib = ctypes.CDLL(_LIB_PATH)
-    P, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    IP = ctypes.POINTER(ctypes.c_int)
-    PP = ctypes.POINTER(ctypes.c_void_p)
-    lib.oflow_abi_version.restype = I
-    lib.oflow_abi_version.argtypes = []
-    lib.oflow_status_string.restype = ctypes.c_char_p
-    lib.oflow_status_string.argtypes = [I]
-    lib.oflow_corr_pyramid_dims.restype = I
-    lib.oflow_corr_pyramid_dims.argtypes = [I, I, I, IP, IP]
-    lib.oflow_corr_pyramid_f32.restype = I
-    lib.oflow_corr_pyramid_f32.argtypes = [P, P, I, I, I, I, I, PP, P]
-    lib.oflow_corr_lookup_f32.restype = I
-    lib.oflow_corr_lookup_f32.argtypes = [PP, IP, IP, I, P, I, I, I, I, P, P]
-    lib.oflow_corr_tiled_level_floats.restype = ctypes.c_longlong
-    lib.oflow_corr_tiled_level_floats.argtypes = [I, I]
-    lib.oflow_corr_pyramid_tiled_f32.restype = I
-    lib.oflow_corr_pyramid_tiled_f32.argtypes = [P, P, I, I, I, I, I, PP, P]
-    lib.oflow_corr_lookup_tiled_f32.restype = I
-    lib.oflow_corr_lookup_tiled_f32.argtypes = [PP, IP, IP, I, P, I, I, I, I, P, P]
-    lib.oflow_corr_untile_f32.restype = I
-    lib.oflow_corr_untile_f32.argtypes = [P, P, ctypes.c_longlong, I, I, P]
-    lib.oflow_grid_warp_f32.restype = I
-    lib.oflow_grid_warp_f32.argtypes = [P, P, I, I, I, I, I, I, I, P, P]
-    lib.oflow_grid_sample_f32.restype = I
-    lib.oflow_grid_sample_f32.argtypes = [P, P, I, I, I, I, I, I, I, I, I, P, P]
-    lib.oflow_corr_otf_prepare_f16.restype = I
-    lib.oflow_corr_otf_prepare_f16.argtypes = [P, P, I, I, I, I, I, P, PP, P, P]
-    L = ctypes.c_longlong
-    lib.oflow_bias_act_f32.restype = I
-    lib.oflow_bias_act_f32.argtypes = [P, L, P, P, L, P, L, I, I, I, I, F, P]
-    lib.oflow_gru_reset_f32.restype = I
-    lib.oflow_gru_reset_f32.argtypes = [P, L, P, P, L, P, L, I, I, I, P]
-    lib.oflow_gru_blend_f32.restype = I
-    lib.oflow_gru_blend_f32.argtypes = [P, L, P, P, L, P, P, L, I, I, I, P]
-    lib.oflow_conv_s32.restype = I
-    lib.oflow_conv_s32.argtypes = [ctypes.POINTER(ConvS32Desc), P]
-    lib.oflow_stem_patches_s32.restype = I
-    lib.oflow_stem_patches_s32.argtypes = [P, I, I, I, I, P, I, P]
-    lib.oflow_norm_stats_finalize.restype = I
-    lib.oflow_norm_stats_finalize.argtypes = [P, I, I, I, I, ctypes.c_double, P, P, P]
-    lib.oflow_norm_apply_s32.restype = I
-    lib.oflow_norm_apply_s32.argtypes = [P, I, I, I, I, P, P, I, I, P, L, P, P, P, I, I, P, L, P]
-    lib.oflow_pack_s32_f32.restype = I
-    lib.oflow_pack_s32_f32.argtypes = [P, L, I, I, I, I, I, I, P, L, P, L, P, I, P]
-    lib.oflow_flow_prep_s32.restype = I
-    lib.oflow_flow_prep_s32.argtypes = [P, I, I, I, P, P, L, P, L, P]
-    lib.oflow_corr_lookup_otf_f16.restype = I
-    lib.oflow_corr_lookup_otf_f16.argtypes = [P, PP, IP, IP, I, P, I, I, I, I, I, P, P]
-    lib.oflow_normalize_images_f32.restype = I
-    lib.oflow_normalize_images_f32.argtypes = [P, P, L, P, P, P]
-    lib.oflow_replicate_pad_f32.restype = I
-    lib.oflow_replicate_pad_f32.argtypes = [P, P, I, L, I, I, I, I, I, I, P]
-    lib.oflow_corr_lookup_backward_f32.restype = I
-    lib.oflow_corr_lookup_backward_f32.argtypes = [P, P, I, I, I, I, PP, IP, IP, I, P]
-    lib.oflow_corr_pyramid_grad_combine_f32.restype = I
-    lib.oflow_corr_pyramid_grad_combine_f32.argtypes = [PP, IP, IP, I, L, P]
-    lib.oflow_corr_lookup_tiled_nhwc_f32.restype = I
-    lib.oflow_corr_lookup_tiled_nhwc_f32.argtypes = [PP, IP, IP, I, P, I, I, I, I, P, I, P]
-    lib.oflow_convex_upsample_f32.restype = I
-    lib.oflow_flow_head2_s32.restype = I
-    lib.oflow_flow_head2_s32.argtypes = [P, ctypes.c_longlong, I, P, P, I, I, I, P, P]
-    lib.oflow_flow_head2_tiled_s32.restype = I
-    lib.oflow_flow_head2_tiled_s32.argtypes = [P, ctypes.c_longlong, I, P, P, I, I, I, P, P]
-    lib.oflow_corr_pyramid_tiled_s32.restype = I
-    lib.oflow_corr_pyramid_tiled_s32.argtypes = [P, P, I, I, I, I, I, PP, P]
-    lib.oflow_corr_lookup_convc1_s32.restype = I
-    lib.oflow_corr_lookup_convc1_s32.argtypes = [PP, IP, IP, I, P, I, I, I, I, P, P, P, P, ctypes.c_longlong, P]
-    lib.oflow_convex_upsample_f32.argtypes = [P, P, I, I, I, P, P]
-    lib.oflow_flow_stats_f32.restype = I
-    lib.oflow_flow_stats_f32.argtypes = [P, I, I, I, I, F, F, I, P, P]
-    lib.oflow_flow2rgb_f32.restype = I
-    lib.oflow_flow2rgb_f32.argtypes = [P, I, I, I, I, I, F, F, I, I, F, P, P, P]
-    lib.oflow_flow_pack_f32.restype = I
-    lib.oflow_flow_pack_f32.argtypes = [P, I, I, I, I, I, P, P]
-    lib.oflow_set_range_flag.restype = I
-    lib.oflow_set_range_flag.argtypes = [P]
-    lib.oflow_range_flag_exchange.restype = I
-    lib.oflow_range_flag_exchange.argtypes = [P, P, P]
-    lib.oflow_timing_event_create.restype = I
-    lib.oflow_timing_event_create.argtypes = [ctypes.POINTER(ctypes.c_void_p)]
-    lib.oflow_timing_event_destroy.restype = I
-    lib.oflow_timing_event_destroy.argtypes = [P]
-    lib.oflow_timing_event_record.restype = I
-    lib.oflow_timing_event_record.argtypes = [P, P, I]
-    lib.oflow_timing_event_elapsed_ms.restype = I
-    lib.oflow_timing_event_elapsed_ms.argtypes = [P, P, ctypes.POINTER(ctypes.c_float)]
-    lib.oflow_flow_head_col2im_f32.restype = I
-    lib.oflow_flow_head_col2im_f32.argtypes = [P, P, I, I, I, P, P]
-    lib.oflow_flow_head_finish_f32.restype = I
-    lib.oflow_flow_head_finish_f32.argtypes = [P, I, P, I, I, I, P, P, L, P, L, P]
-    FP = ctypes.POINTER(F)
-    lib.oflow_flow_error_stats_f32.restype = I
-    lib.oflow_flow_error_stats_f32.argtypes = [P, L, L, L, P, L, L, L, P, I, L, L, I, I, I, F, F, F, P, P, P, P]
-    lib.oflow_sequence_loss_f32.restype = I
-    lib.oflow_sequence_loss_f32.argtypes = [PP, I, FP, P, P, I, I, I, I, F, P, P, P, P]
-    lib.oflow_sequence_loss_backward_f32.restype = I
-    lib.oflow_sequence_loss_backward_f32.argtypes = [P, PP, PP, I, FP, P, P, I, I, I, I, F, P]
-    lib.oflow_convex_upsample_backward_f32.restype = I
-    lib.oflow_convex_upsample_backward_f32.argtypes = [P, P, P, I, I, I, P, P, P, P]
-    lib.oflow_corr_lookup_otf_backward_f32.restype = I
-    lib.oflow_corr_lookup_otf_backward_f32.argtypes = [P, P, PP, IP, IP, I, P, I, I, I, I, I, P, P, P, P]
-    lib.oflow_forward_interpolate_f32.restype = I
-    lib.oflow_forward_interpolate_f32.argtypes = [P, I, I, I, P, P]
-    lib.oflow_augment_stats_u8.restype = I
-    lib.oflow_augment_stats_u8.argtypes = [P, P, P, I, I, I, I, P, P]
-    lib.oflow_augment_dense_f32.restype = I
-    lib.oflow_augment_dense_f32.argtypes = [P, P, P, P, P, I, I, I, I, I, P, P, P, P, P]
-    lib.oflow_augment_sparse_flow_f32.restype = I
-    lib.oflow_augment_sparse_flow_f32.argtypes = [P, P, P, I, I, I, I, I, P, P, P]
-    lib.oflow_conv2d_backward_input_f32.restype = I
-    lib.oflow_conv2d_backward_input_f32.argtypes = [P, P, I, I, I, I, I, I, I, P, P]
-    lib.oflow_conv2d_backward_weight_slab_pixels.restype = I
-    lib.oflow_conv2d_backward_weight_slab_pixels.argtypes = []
-    lib.oflow_conv2d_backward_weight_workspace_floats.restype = L
-    lib.oflow_conv2d_backward_weight_workspace_floats.argtypes = [I, I, I, I, I, I, I]
-    lib.oflow_conv2d_backward_weight_f32.restype = I
-    lib.oflow_conv2d_backward_weight_f32.argtypes = [P, P, I, I, I, I, I, I, I, P, P, P, P]
-    lib.oflow_conv2d_strided_backward_input_f32.restype = I
-    lib.oflow_conv2d_strided_backward_input_f32.argtypes = [P, P, I, I, I, I, I, I, I, I, P, P]
-    lib.oflow_conv2d_strided_backward_weight_workspace_floats.restype = L
-    lib.oflow_conv2d_strided_backward_weight_workspace_floats.argtypes = [I, I, I, I, I, I, I, I]
-    for fn in (lib.oflow_conv2d_strided_backward_weight_f32, lib.oflow_conv2d_strided_backward_weight_generic_f32):
-        fn.restype = I
-        fn.argtypes = [P, P, I, I, I, I, I, I, I, I, P, P, P, P]
-    lib.oflow_instance_norm_backward_f32.restype = I
-    lib.oflow_instance_norm_backward_f32.argtypes = [P, P, I, I, ctypes.c_double, I, P, P]
-    lib.oflow_frozen_batch_norm_backward_workspace_floats.restype = L
-    lib.oflow_frozen_batch_norm_backward_workspace_floats.argtypes = [I, I, I]
-    lib.oflow_frozen_batch_norm_backward_f32.restype = I
-    lib.oflow_frozen_batch_norm_backward_f32.argtypes = [P, P, P, P, P, P, I, I, I, ctypes.c_double, I, P, P, P, P, P]
-    lib.oflow_batch_norm_chunk_elements.restype = I
-    lib.oflow_batch_norm_chunk_elements.argtypes = []
-    lib.oflow_batch_norm_workspace_floats.restype = L
-    lib.oflow_batch_norm_workspace_floats.argtypes = [I, I, I]
-    lib.oflow_batch_norm_forward_f32.restype = I
-    lib.oflow_batch_norm_forward_f32.argtypes = [P, P, P, I, I, I, ctypes.c_double, I, P, P, P, P, P]
-    lib.oflow_batch_norm_backward_f32.restype = I
-    lib.oflow_batch_norm_backward_f32.argtypes = [P, P, P, P, P, P, I, I, I, ctypes.c_double, I, P, P, P, P, P]
-    lib.oflow_fb_consistency_f32.restype = I
-    lib.oflow_fb_consistency_f32.argtypes = [P, P, I, I, I, F, F, P, P, P, P, P]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     v = lib.oflow_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"liboflow_hip.so ABI version {v}, expected {ABI_VERSION}: rebuild the library")

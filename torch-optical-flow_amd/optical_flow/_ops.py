@@ -164,38 +164,24 @@ def _lookup_backward(ctx, grad_out):
     return list(grads), None, None
 
 
-def _warp_setup(ctx, inputs, output):
-    frame, flow, mode, pad, ac = inputs
-    ctx.save_for_backward(frame, flow)
-    ctx.args = (mode, pad, ac)
+def _sampler_formula(backward_op):
+    """(setup_context, backward) of ``grid_warp`` (frame, flow) and ``grid_sample`` (input, grid): the same formula over
+    (source, field, mode, padding_mode, align_corners), with the op's own native transpose."""
 
+    def setup(ctx, inputs, output):
+        src, field, mode, pad, ac = inputs
+        ctx.save_for_backward(src, field)
+        ctx.args = (mode, pad, ac)
 
-def _warp_backward(ctx, grad_out):
-    frame, flow = ctx.saved_tensors
-    mode, pad, ac = ctx.args
-    # the native transpose (warp_backward.hip): grid = linspace base + flow, so the flow gradient is the grid gradient
-    # only the wanted outputs are formed (no zero fill / atomics for a frame that needs no gradient)
-    need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])]
-    g_in, g_flow = torch.ops.oflow.grid_warp_backward(grad_out.contiguous(), frame, flow, mode, pad, ac, need)
-    g_frame = g_in.to(frame.dtype) if need[0] else None
-    g_flow = g_flow.to(flow.dtype) if need[1] else None
-    return g_frame, g_flow, None, None, None
+    def backward(ctx, grad_out):
+        src, field = ctx.saved_tensors
+        # the native transpose (warp_backward.hip): a warp's grid = linspace base + flow, so its flow gradient is the
+        # grid gradient. Only the wanted outputs are formed (no zero fill / atomics for a source that needs no gradient)
+        need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])]
+        g_src, g_field = backward_op(grad_out.contiguous(), src, field, *ctx.args, need)
+        return (g_src.to(src.dtype) if need[0] else None), (g_field.to(field.dtype) if need[1] else None), None, None, None
 
-
-def _sample_setup(ctx, inputs, output):
-    inp, grid, mode, pad, ac = inputs
-    ctx.save_for_backward(inp, grid)
-    ctx.args = (mode, pad, ac)
-
-
-def _sample_backward(ctx, grad_out):
-    inp, grid = ctx.saved_tensors
-    mode, pad, ac = ctx.args
-    need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])]
-    g_in, g_grid = torch.ops.oflow.grid_sample_backward(grad_out.contiguous(), inp, grid, mode, pad, ac, need)
-    g_x = g_in.to(inp.dtype) if need[0] else None
-    g_g = g_grid.to(grid.dtype) if need[1] else None
-    return g_x, g_g, None, None, None
+    return setup, backward
 
 
 def _seqloss_setup(ctx, inputs, output):
@@ -226,32 +212,33 @@ def _upsample_backward(ctx, grad_out):
     return (g_flow.to(flow.dtype) if need[0] else None), (g_mask.to(mask.dtype) if need[1] else None)
 
 
-def _conv_setup(ctx, inputs, output):
-    x, weight, bias = inputs
-    ctx.save_for_backward(x, weight)
-    ctx.has_bias = bias is not None
+def _param_layer_formula(backward_op, n_saved, n_plain, saves_statistics=False):
+    """(setup_context, backward) of the layers with an (x, weight, bias) gradient: ``conv2d_same`` / ``conv2d_strided``
+    and ``frozen_batch_norm_act`` / ``batch_norm_act``. Their inputs are (x, weight, bias, further tensors..., then
+    ``n_plain`` non-tensor arguments) and their backward op takes (grad_out, saved tensors..., non-tensor arguments...,
+    output_mask) -> (grad_x, grad_weight, grad_bias).
 
+    ``n_saved``: how many leading inputs are saved: 2 for the convolutions (x and weight; of the bias only whether there
+    is one), all the tensors for the norms. ``saves_statistics``: the outputs after the first (``batch_norm_act``'s mean
+    and var, as the forward returned them: C floats each) are saved too and are not differentiable."""
 
-def _conv_backward(ctx, grad_out):
-    x, weight = ctx.saved_tensors
-    need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]), ctx.has_bias and bool(ctx.needs_input_grad[2])]
-    # (a stride-0 expanded gradient, what .sum() hands over, becomes a real tensor here)
-    g_x, g_w, g_b = torch.ops.oflow.conv2d_same_backward(grad_out.contiguous(), x, weight, need)
-    return (g_x if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None)
+    def setup(ctx, inputs, output):
+        saved = tuple(inputs[:n_saved])
+        if saves_statistics:
+            saved += tuple(output[1:])
+            ctx.mark_non_differentiable(*output[1:])
+        ctx.save_for_backward(*saved)
+        ctx.has_bias = inputs[2] is not None
+        ctx.plain = tuple(inputs[len(inputs) - n_plain:])
+        ctx.n_inputs = len(inputs)
 
+    def backward(ctx, grad_out, *_grad_statistics):
+        need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]), ctx.has_bias and bool(ctx.needs_input_grad[2])]
+        # (a stride-0 expanded gradient, what .sum() hands over, becomes a real tensor here)
+        grads = backward_op(grad_out.contiguous(), *ctx.saved_tensors, *ctx.plain, need)
+        return tuple(g if n else None for g, n in zip(grads, need)) + (None,) * (ctx.n_inputs - 3)
 
-def _sconv_setup(ctx, inputs, output):
-    x, weight, bias, stride = inputs
-    ctx.save_for_backward(x, weight)
-    ctx.has_bias = bias is not None
-    ctx.stride = stride
-
-
-def _sconv_backward(ctx, grad_out):
-    x, weight = ctx.saved_tensors
-    need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]), ctx.has_bias and bool(ctx.needs_input_grad[2])]
-    g_x, g_w, g_b = torch.ops.oflow.conv2d_strided_backward(grad_out.contiguous(), x, weight, ctx.stride, need)
-    return (g_x if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None), None
+    return setup, backward
 
 
 def _inorm_setup(ctx, inputs, output):
@@ -264,38 +251,6 @@ def _inorm_backward(ctx, grad_out):
     (x,) = ctx.saved_tensors
     eps, relu = ctx.args
     return torch.ops.oflow.instance_norm_act_backward(grad_out.contiguous(), x, eps, relu), None, None
-
-
-def _fbn_setup(ctx, inputs, output):
-    x, weight, bias, rmean, rvar, eps, relu = inputs
-    ctx.save_for_backward(x, weight, bias, rmean, rvar)
-    ctx.args = (eps, relu)
-
-
-def _fbn_backward(ctx, grad_out):
-    x, weight, bias, rmean, rvar = ctx.saved_tensors
-    eps, relu = ctx.args
-    need = [bool(n) for n in ctx.needs_input_grad[:3]]
-    g_x, g_w, g_b = torch.ops.oflow.frozen_batch_norm_act_backward(grad_out.contiguous(), x, weight, bias, rmean, rvar,
-                                                                   eps, relu, need)
-    return (g_x if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None), None, None, None, None
-
-
-def _bn_setup(ctx, inputs, output):
-    x, weight, bias, eps, relu = inputs
-    _y, mean, var = output
-    ctx.save_for_backward(x, weight, bias, mean, var)  # the statistics as the forward returned them: C floats each
-    ctx.args = (eps, relu)
-    ctx.mark_non_differentiable(mean, var)
-
-
-def _bn_backward(ctx, grad_out, _grad_mean, _grad_var):
-    x, weight, bias, mean, var = ctx.saved_tensors
-    eps, relu = ctx.args
-    need = [bool(n) for n in ctx.needs_input_grad[:3]]
-    g_x, g_w, g_b = torch.ops.oflow.batch_norm_act_backward(grad_out.contiguous(), x, weight, bias, mean, var, eps, relu,
-                                                            need)
-    return (g_x if need[0] else None), (g_w if need[1] else None), (g_b if need[2] else None), None, None
 
 
 def _alt_setup(ctx, inputs, output):
@@ -315,16 +270,21 @@ def _alt_backward(ctx, grad_out):
 
 
 def _register_autograd() -> None:
-    reg = torch.library.register_autograd
-    reg("oflow::corr_pyramid", _pyramid_backward, setup_context=_pyramid_setup)
-    reg("oflow::corr_lookup", _lookup_backward, setup_context=_lookup_setup)
-    reg("oflow::grid_warp", _warp_backward, setup_context=_warp_setup)
-    reg("oflow::grid_sample", _sample_backward, setup_context=_sample_setup)
-    reg("oflow::sequence_loss", _seqloss_backward, setup_context=_seqloss_setup)
-    reg("oflow::convex_upsample", _upsample_backward, setup_context=_upsample_setup)
-    reg("oflow::corr_lookup_alt", _alt_backward, setup_context=_alt_setup)
-    reg("oflow::conv2d_same", _conv_backward, setup_context=_conv_setup)
-    reg("oflow::conv2d_strided", _sconv_backward, setup_context=_sconv_setup)
-    reg("oflow::instance_norm_act", _inorm_backward, setup_context=_inorm_setup)
-    reg("oflow::frozen_batch_norm_act", _fbn_backward, setup_context=_fbn_setup)
-    reg("oflow::batch_norm_act", _bn_backward, setup_context=_bn_setup)
+    ops = torch.ops.oflow
+
+    def reg(name, setup, backward):
+        torch.library.register_autograd(name, backward, setup_context=setup)
+
+    reg("oflow::corr_pyramid", _pyramid_setup, _pyramid_backward)
+    reg("oflow::corr_lookup", _lookup_setup, _lookup_backward)
+    reg("oflow::grid_warp", *_sampler_formula(ops.grid_warp_backward))
+    reg("oflow::grid_sample", *_sampler_formula(ops.grid_sample_backward))
+    reg("oflow::sequence_loss", _seqloss_setup, _seqloss_backward)
+    reg("oflow::convex_upsample", _upsample_setup, _upsample_backward)
+    reg("oflow::corr_lookup_alt", _alt_setup, _alt_backward)
+    reg("oflow::conv2d_same", *_param_layer_formula(ops.conv2d_same_backward, n_saved=2, n_plain=0))
+    reg("oflow::conv2d_strided", *_param_layer_formula(ops.conv2d_strided_backward, n_saved=2, n_plain=1))
+    reg("oflow::instance_norm_act", _inorm_setup, _inorm_backward)
+    reg("oflow::frozen_batch_norm_act", *_param_layer_formula(ops.frozen_batch_norm_act_backward, n_saved=5, n_plain=2))
+    reg("oflow::batch_norm_act",
+        *_param_layer_formula(ops.batch_norm_act_backward, n_saved=3, n_plain=2, saves_statistics=True))
