@@ -37,6 +37,8 @@
  *   oflow_fb_consistency_f32 <- nothing in the reference (csrc/fb_consistency.hip): the forward-backward occlusion
  *                              mask of a flow pair, UnFlow's criterion (Meister et al., whom the reference cites for
  *                              optical_flow/visualization/methods/meister.py)
+ *   oflow_splat_f32, oflow_splat_backward_f32 <- nothing in the reference (csrc/splat.hip, csrc/splat_backward.hip):
+ *                              forward warping, the sum / average / linear / softmax splatting of Niklaus and Liu
  *   oflow_augment_stats_u8, oflow_augment_dense_f32, oflow_augment_sparse_flow_f32 <- methods/raft/data/augmentor.py:43-324
  *                              (FlowAugmentor, SparseFlowAugmentor: PIL ColorJitter, cv2.resize, eraser, flips, crop)
  *                              + methods/raft/data/dataset.py:114-119 (fp32 flow, the dense valid mask)
@@ -698,6 +700,75 @@ int oflow_forward_interpolate_f32(const float* d_flow, int B, int H, int W, floa
  */
 int oflow_fb_consistency_f32(const float* d_fw, const float* d_bw, int B, int H, int W, float alpha, float beta,
                              unsigned char* d_mask_fw, unsigned char* d_mask_bw, float* d_err_fw, float* d_err_bw,
+                             void* stream);
+
+/*
+ * Forward warping / splatting (csrc/splat.hip, csrc/splat_backward.hip): summation, average, linear and softmax
+ * splatting (Niklaus and Liu, CVPR 2020) of a frame along a flow in pixel units, deterministic in both directions. The
+ * reference has no such function.
+ * oflow_splat_f32: d_frame (B, C, H, W), d_flow (B, 2, H, W) (channel 0 = dx, 1 = dy), d_metric (B, 1, H, W) or NULL,
+ *   all contiguous fp32; outputs d_out (B, C, H, W) and d_weight (B, 1, H, W) fp32, both required. mode:
+ *     OFLOW_SPLAT_SUM     m = 1, out = N            (d_metric must be NULL, else OFLOW_E_MODE)
+ *     OFLOW_SPLAT_AVG     m = 1, out = N / (D + EPS) (d_metric must be NULL, else OFLOW_E_MODE)
+ *     OFLOW_SPLAT_LINEAR  m = metric (expected >= 0), out = N / (D + EPS)   (d_metric required, else OFLOW_E_NULL)
+ *     OFLOW_SPLAT_SOFT    m = expf(fp32(metric - M_b)), M_b the maximum of image b's metric, out = N / (D + EPS)
+ *   with EPS = OFLOW_SPLAT_EPS = 1e-7. For image b and source pixel s = (i, j) with u = flow[b,0,i,j], v = flow[b,1,i,j]:
+ *     px = float(j) + u, py = float(i) + v (fp32 sums, each rounded once, as oflow_fb_consistency_f32 forms them);
+ *     skipped unless px > -1 && px < W && py > -1 && py < H (false for NaN; tested before any float-to-int
+ *       conversion, so +-inf and 1e30 are skipped too): a skipped source contributes nothing;
+ *     x0 = floorf(px), fx = px - x0 in fp64 (exact), the same in y; the four taps (x0 + dx, y0 + dy), dx, dy in {0, 1},
+ *       have the weights w = ax[dx] * ay[dy] with ax = (1 - fx, fx), ay = (1 - fy, fy), also in fp64; a tap outside
+ *       the frame is dropped on its own;
+ *     N_c(t) = sum of w * m * frame[b,c,s] and D(t) = sum of w * m over every source and tap that meets target t.
+ *   A target that nothing reaches has out = 0 and weight = 0 exactly; d_weight = D marks the holes (for SOFT, D is
+ *   relative to the image's largest weight, which is 1: the shift by M_b keeps expf from overflowing, counts as a
+ *   constant in the gradient, and makes EPS act relative to the image's largest weight -- the paper's form is unshifted).
+ *   Sums are 64-bit fixed point: per image, with F = max |frame[b]| and Mx = max |metric[b]| (LINEAR; 1 otherwise), the
+ *   exponents are eF = frexp exponent of F (F < 2^eF; 0 for F = 0), eM likewise of Mx, eN = eF + eM, eD = eM; every
+ *   contribution is formed in fp64 ((w * m) * frame), multiplied by 2^(K - eN) (N) or 2^(K - eD) (D), rounded to the
+ *   nearest integer (ties to even) and added with a 64-bit integer atomic; K = oflow_splat_frac_bits(H, W) =
+ *   62 - ceil(log2(4 * H * W)) fractional bits (60 for one pixel, OFLOW_SPLAT_MIN_FRAC_BITS = 38 at the largest frame).
+ *   Integer addition is associative: the same bits on every run, and an image's bits do not depend on the rest of the
+ *   batch (its scale is its own). Overflow is impossible: a target receives at most 4 * H * W contributions, each at
+ *   most 2^K in magnitude after scaling, so |sum| <= 4 * H * W * 2^K <= 2^62 < 2^63 (H * W <= OFLOW_SPLAT_MAX_PIXELS
+ *   = 2^22). The finish pass converts each sum to fp64, multiplies by the quantum 2^(eN - K) / 2^(eD - K), divides
+ *   in fp64 and rounds once to fp32. A non-finite frame or metric value makes that image's outputs unspecified (no
+ *   address depends on it; other images are unaffected).
+ *   d_workspace: oflow_splat_workspace_bytes(B, C, H, W) bytes, 8-byte aligned (else OFLOW_E_ALIGN): the planar int64
+ *   accumulators (B, C + 1, H, W) and 4 words per image (range maxima and the two exponents). The library zeroes it
+ *   on the stream; the caller initialises nothing. Every element of both outputs is written.
+ *   NULL d_frame / d_flow / d_out / d_weight / d_workspace: OFLOW_E_NULL. B, C, H or W < 1, B > 65535 or H * W >
+ *   2^22: OFLOW_E_SHAPE (oflow_splat_workspace_bytes and oflow_splat_frac_bits return 0 for these). mode outside
+ *   0..3: OFLOW_E_MODE.
+ * oflow_splat_backward_f32: the gradients of a scalar loss with d_grad_out = dL/dout (B, C, H, W); d_out and d_weight
+ *   are the forward's outputs (not read for SUM). A pure gather, no atomics, every element of a requested output written
+ *   exactly once: bit-identical from run to run, and each output has the same bits whichever others are asked for.
+ *   With r_t = 1 / (D(t) + EPS) and gd_t = -r_t * sum_c g_c(t) * out_c(t) (SUM: r = 1, gd = 0), per source s and its
+ *   taps t (dropped taps contribute nothing, a skipped source gets zeros):
+ *     G_c = sum_t w_t r_t g_c(t);  GD = sum_t w_t gd_t;  grad_frame[c] = m * G_c;  g_m = sum_c frame_c G_c + GD;
+ *     grad_metric = g_m (LINEAR), m * g_m (SOFT; M_b counts as a constant);
+ *     grad_flow[x] = m * sum_t (dw_t/dpx) q_t, q_t = sum_c frame_c r_t g_c(t) + gd_t, dw_t/dpx = -ay[dy] (dx = 0),
+ *     +ay[dy] (dx = 1); the same in y. The floor convention fixes the one-sided derivative at integer positions, as
+ *     grid_sample's backward does. fp32 arithmetic.
+ *   d_grad_frame (B, C, H, W), d_grad_flow (B, 2, H, W), d_grad_metric (B, 1, H, W): a NULL output is not formed (all
+ *   three NULL, or d_grad_metric given for SUM / AVG: OFLOW_E_NULL / OFLOW_E_MODE). d_workspace: the same size as the
+ *   forward's (its first 8 * B * H * W bytes hold the r and gd planes), not zeroed by anyone; may be NULL for SUM.
+ *   The other argument errors are the forward's.
+ */
+#define OFLOW_SPLAT_SUM 0
+#define OFLOW_SPLAT_AVG 1
+#define OFLOW_SPLAT_LINEAR 2
+#define OFLOW_SPLAT_SOFT 3
+#define OFLOW_SPLAT_EPS 1e-7
+#define OFLOW_SPLAT_MIN_FRAC_BITS 38
+#define OFLOW_SPLAT_MAX_PIXELS (1 << 22)
+int oflow_splat_frac_bits(int H, int W);
+long long oflow_splat_workspace_bytes(int B, int C, int H, int W);
+int oflow_splat_f32(const float* d_frame, const float* d_flow, const float* d_metric, int B, int C, int H, int W,
+                    int mode, float* d_out, float* d_weight, void* d_workspace, void* stream);
+int oflow_splat_backward_f32(const float* d_grad_out, const float* d_frame, const float* d_flow, const float* d_metric,
+                             const float* d_out, const float* d_weight, int B, int C, int H, int W, int mode,
+                             float* d_grad_frame, float* d_grad_flow, float* d_grad_metric, void* d_workspace,
                              void* stream);
 
 /*

@@ -42,6 +42,9 @@
 //   augment_batch(img1, img2, flow, valid?, params, crop_h, crop_w) -> (img1, img2, flow, valid)   data/augmentor.py:43-324
 //   fb_consistency(flow_fw, flow_bw, alpha, beta, both, with_error) -> (mask_fw, mask_bw, err_fw, err_bw)
 //                                                                 forward-backward occlusion masks (not in the reference)
+//   splat(frame, flow, metric?, mode) -> (out, weight)           forward warping: sum / average / linear / softmax splatting
+//   splat_backward(grad_out, frame, flow, metric?, out, weight, mode, mask3) -> (grad_frame, grad_flow, grad_metric)
+//                                                                 its autograd (splat.hip, splat_backward.hip; not in the reference)
 #include <array>
 #include <torch/library.h>
 #include <ATen/ATen.h>
@@ -1070,6 +1073,91 @@ Tensor4 fb_consistency(bool run, const Tensor& fw, const Tensor& bw, double alph
   return Tensor4(m_fw, m_bw, e_fw, e_bw);
 }
 
+// ---------------------------------------------------------------- forward warping (splat.hip, splat_backward.hip)
+void check_splat(const Tensor& frame, const Tensor& flow, const c10::optional<Tensor>& metric, int64_t mode, bool run,
+                 const char* what) {
+  if (run) {
+    check_on_gpu(frame, "frame", what), check_on_gpu(flow, "flow", what);
+    if (metric.has_value()) check_on_gpu(*metric, "metric", what);
+  }
+  TORCH_CHECK(frame.dim() == 4, what, ": frame must be (B, C, H, W), got ", frame.sizes());
+  const int64_t b = frame.size(0), c = frame.size(1), h = frame.size(2), w = frame.size(3);
+  TORCH_CHECK(flow.dim() == 4 && flow.size(0) == b && flow.size(1) == 2 && flow.size(2) == h && flow.size(3) == w, what,
+              ": flow must be (B, 2, H, W) = (", b, ", 2, ", h, ", ", w, "), got ", flow.sizes());
+  TORCH_CHECK(flow.device() == frame.device(), what, ": frame and flow are on different devices");
+  TORCH_CHECK(mode >= OFLOW_SPLAT_SUM && mode <= OFLOW_SPLAT_SOFT, what, ": mode ", mode, " outside [0, 3]");
+  const bool metric_mode = mode == OFLOW_SPLAT_LINEAR || mode == OFLOW_SPLAT_SOFT;
+  TORCH_CHECK(metric.has_value() == metric_mode, what, ": mode ", mode,
+              metric_mode ? " needs a metric" : " takes no metric");
+  if (metric_mode) {
+    TORCH_CHECK(metric->dim() == 4 && metric->size(0) == b && metric->size(1) == 1 && metric->size(2) == h &&
+                    metric->size(3) == w,
+                what, ": metric must be (B, 1, H, W) = (", b, ", 1, ", h, ", ", w, "), got ", metric->sizes());
+    TORCH_CHECK(metric->device() == frame.device(), what, ": frame and metric are on different devices");
+  }
+  TORCH_CHECK(b <= 65535 && c <= INT_MAX && h * w <= OFLOW_SPLAT_MAX_PIXELS, what, ": frame ", frame.sizes(),
+              " is past the kernels' range (B <= 65535, H*W <= 2^22)");
+}
+
+// (out (B, C, H, W), weight (B, 1, H, W)) fp32; any float dtype or strides, as warp
+std::tuple<Tensor, Tensor> splat(bool run, const Tensor& frame, const Tensor& flow, const c10::optional<Tensor>& metric,
+                                 int64_t mode) {
+  const char* what = "splat";
+  check_splat(frame, flow, metric, mode, run, what);
+  const int64_t b = frame.size(0), c = frame.size(1), h = frame.size(2), w = frame.size(3);
+  const auto opt = frame.options().dtype(at::kFloat);
+  Tensor out = at::empty({b, c, h, w}, opt), weight = at::empty({b, 1, h, w}, opt);
+  if (!run || out.numel() == 0) {
+    if (run) weight.zero_();  // (C = 0 with pixels: nothing lands anywhere)
+    return {out, weight};
+  }
+  Tensor fr = gpu_f32(frame, "frame", what), fl = gpu_f32(flow, "flow", what), me;
+  if (metric.has_value()) me = gpu_f32(*metric, "metric", what);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(fr.device());
+  Tensor ws = at::empty({oflow_splat_workspace_bytes((int)b, (int)c, (int)h, (int)w) / 8}, opt.dtype(at::kLong));
+  check_status(oflow_splat_f32(fr.data_ptr<float>(), fl.data_ptr<float>(), me.defined() ? me.data_ptr<float>() : nullptr,
+                               (int)b, (int)c, (int)h, (int)w, (int)mode, out.data_ptr<float>(),
+                               weight.data_ptr<float>(), ws.data_ptr<int64_t>(), cur_stream()),
+               what);
+  return {out, weight};
+}
+
+Tensor3 splat_backward(bool run, const Tensor& gout, const Tensor& frame, const Tensor& flow,
+                       const c10::optional<Tensor>& metric, const Tensor& out, const Tensor& weight, int64_t mode,
+                       std::array<bool, 3> om) {
+  const char* what = "splat backward";
+  if (run) check_on_gpu(gout, "grad_out", what);
+  check_splat(frame, flow, metric, mode, run, what);
+  const int64_t b = frame.size(0), c = frame.size(1), h = frame.size(2), w = frame.size(3);
+  TORCH_CHECK(gout.sizes() == frame.sizes() && out.sizes() == frame.sizes(), what, ": grad_out ", gout.sizes(), " and out ",
+              out.sizes(), " must have frame's shape ", frame.sizes());
+  TORCH_CHECK(weight.dim() == 4 && weight.size(0) == b && weight.size(1) == 1 && weight.size(2) == h && weight.size(3) == w,
+              what, ": weight must be (B, 1, H, W), got ", weight.sizes());
+  TORCH_CHECK(gout.device() == frame.device() && out.device() == frame.device() && weight.device() == frame.device(), what,
+              ": all tensors must be on one device");
+  TORCH_CHECK(!om[2] || metric.has_value(), what, ": a metric gradient needs a metric");
+  const auto opt = frame.options().dtype(at::kFloat);
+  Tensor gfr = wanted(om[0], {b, c, h, w}, opt), gfl = wanted(om[1], {b, 2, h, w}, opt), gme = wanted(om[2], {b, 1, h, w}, opt);
+  if (!run || !(om[0] || om[1] || om[2])) return Tensor3(gfr, gfl, gme);
+  if (frame.numel() == 0) {
+    if (om[1]) gfl.zero_();
+    if (om[2]) gme.zero_();
+    return Tensor3(gfr, gfl, gme);
+  }
+  Tensor go = gpu_f32(gout, "grad_out", what), fr = gpu_f32(frame, "frame", what), fl = gpu_f32(flow, "flow", what);
+  Tensor ou = gpu_f32(out, "out", what), we = gpu_f32(weight, "weight", what), me;
+  if (metric.has_value()) me = gpu_f32(*metric, "metric", what);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(fr.device());
+  Tensor ws = at::empty({oflow_splat_workspace_bytes((int)b, (int)c, (int)h, (int)w) / 8}, opt.dtype(at::kLong));
+  check_status(oflow_splat_backward_f32(go.data_ptr<float>(), fr.data_ptr<float>(), fl.data_ptr<float>(),
+                                        me.defined() ? me.data_ptr<float>() : nullptr, ou.data_ptr<float>(),
+                                        we.data_ptr<float>(), (int)b, (int)c, (int)h, (int)w, (int)mode,
+                                        om[0] ? gfr.data_ptr<float>() : nullptr, om[1] ? gfl.data_ptr<float>() : nullptr,
+                                        om[2] ? gme.data_ptr<float>() : nullptr, ws.data_ptr<int64_t>(), cur_stream()),
+               what);
+  return Tensor3(gfr, gfl, gme);
+}
+
 // ---------------------------------------------------------------- training-batch augmentation (augment.hip)
 Tensor4 augment_batch(bool run, const Tensor& img1, const Tensor& img2, const Tensor& flow,
                       const c10::optional<Tensor>& valid, const Tensor& params, int64_t ch, int64_t cw) {
@@ -1187,6 +1275,8 @@ TORCH_LIBRARY(oflow, m) {
   m.def("forward_interpolate(Tensor flow) -> Tensor");
   m.def("augment_batch(Tensor img1, Tensor img2, Tensor flow, Tensor? valid, Tensor params, int crop_h, int crop_w) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("fb_consistency(Tensor flow_fw, Tensor flow_bw, float alpha, float beta, bool both, bool with_error) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("splat(Tensor frame, Tensor flow, Tensor? metric, int mode) -> (Tensor out, Tensor weight)");
+  m.def("splat_backward(Tensor grad_out, Tensor frame, Tensor flow, Tensor? metric, Tensor out, Tensor weight, int mode, bool[3] output_mask) -> (Tensor, Tensor, Tensor)");
 
   bind<&corr_pyramid>(m, "corr_pyramid");
   bind<&corr_pyramid_tiled>(m, "corr_pyramid_tiled");
@@ -1221,4 +1311,6 @@ TORCH_LIBRARY(oflow, m) {
   bind<&forward_interpolate>(m, "forward_interpolate");
   bind<&augment_batch>(m, "augment_batch");
   bind<&fb_consistency>(m, "fb_consistency");
+  bind<&splat>(m, "splat");
+  bind<&splat_backward>(m, "splat_backward");
 }

@@ -4,11 +4,14 @@ Re-exports the operator API of the reference (`optical_flow/__init__.py:2`). ``w
 gfx950 HIP kernel through the C ABI of ``liboflow_hip.so`` (include/oflow.h). The inference I/O of the reference
  is here too: ``flow2rgb``/``colorwheel`` on a fused colour-map kernel and ``read``/``write``
 (Middlebury, PFM, KITTI) with the file payload laid out on the device. ``fb_consistency`` (an addition) gives the
-forward-backward occlusion masks of a flow pair in one kernel launch.
+forward-backward occlusion masks of a flow pair in one kernel launch; ``splat`` (an addition) warps a frame forwards
+along a flow (sum / average / linear / softmax splatting, bit-reproducible, differentiable) and ``interpolate_frame``
+blends two such warps into an in-between frame.
 """
 from .io.read_write import read, write
-from .operator.operator import denormalize, fb_consistency, integrate, normalize, resize, scale, warp, warp_grid
+from .operator.operator import (denormalize, fb_consistency, integrate, interpolate_frame, normalize, resize, scale, splat,
+                                warp, warp_grid)
 from .visualization.flow2rgb import colorwheel, flow2rgb
 
-__all__ = ["colorwheel", "denormalize", "fb_consistency", "flow2rgb", "integrate", "normalize", "read", "resize", "scale",
-           "warp", "warp_grid", "write"]
+__all__ = ["colorwheel", "denormalize", "fb_consistency", "flow2rgb", "integrate", "interpolate_frame", "normalize", "read",
+           "resize", "scale", "splat", "warp", "warp_grid", "write"]

@@ -127,6 +127,10 @@ def _signatures():
         "oflow_batch_norm_forward_f32": (I, [P, P, P, I, I, I, D, I, P, P, P, P, P]),
         "oflow_batch_norm_backward_f32": (I, [P, P, P, P, P, P, I, I, I, D, I, P, P, P, P, P]),
         "oflow_fb_consistency_f32": (I, [P, P, I, I, I, F, F, P, P, P, P, P]),
+        "oflow_splat_frac_bits": (I, [I, I]),
+        "oflow_splat_workspace_bytes": (L, [I, I, I, I]),
+        "oflow_splat_f32": (I, [P, P, P, I, I, I, I, I, P, P, P, P]),
+        "oflow_splat_backward_f32": (I, [P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P]),
     }
 
 
@@ -466,6 +470,27 @@ def fb_consistency(flow_fw: torch.Tensor, flow_bw: torch.Tensor, alpha: float, b
     fw, bw = _tensor(flow_fw, "flow_fw", what), _tensor(flow_bw, "flow_bw", what)
     return _run(what, fw.device, ops().fb_consistency, fw.detach(), bw.detach(), float(alpha), float(beta), bool(both),
                 bool(with_error))
+
+
+SPLAT_MODES = {"sum": 0, "avg": 1, "linear": 2, "soft": 3}  # include/oflow.h OFLOW_SPLAT_*
+SPLAT_EPS = 1e-7  # include/oflow.h OFLOW_SPLAT_EPS
+
+
+def splat_frac_bits(h: int, w: int) -> int:
+    """The fixed-point sums' fractional bits for an (H, W) frame: 62 - ceil(log2(4 H W)) (oflow_splat_frac_bits)."""
+    return int(load().oflow_splat_frac_bits(h, w))
+
+
+def splat(frame: torch.Tensor, flow: torch.Tensor, metric: Optional[torch.Tensor], mode: str):
+    """Forward warping of a (B, C, H, W) frame along a (B, 2, H, W) flow in pixel units (``torch.ops.oflow.splat``,
+    include/oflow.h oflow_splat_f32): (out (B, C, H, W), weight (B, 1, H, W)) fp32, bit-reproducible. Differentiable in
+    frame, flow and metric (native gather, csrc/splat_backward.hip); the weight is not."""
+    what = "splat"
+    if mode not in SPLAT_MODES:
+        raise ValueError(f"{what}: unknown mode {mode!r} (one of {sorted(SPLAT_MODES)})")
+    fr, fl = _tensor(frame, "frame", what), _tensor(flow, "flow", what)
+    me = None if metric is None else _tensor(metric, "metric", what)
+    return _run(what, fr.device, ops().splat, fr, fl, me, SPLAT_MODES[mode])
 
 
 AUG_PARAM_DOUBLES = 36  # include/oflow.h OFLOW_AUG_PARAM_DOUBLES

@@ -56,6 +56,12 @@ in float64, piecewise constant in its input; callers detach the input, ``model.u
 nor has ``fb_consistency`` (the forward-backward occlusion masks, csrc/fb_consistency.hip): a mask is piecewise constant
 in the flows and has no gradient, and the residual is returned for inspection and thresholding, not for a loss, so
 ``optical_flow.fb_consistency`` detaches its inputs.
+  * ``splat`` (``optical_flow.splat``, forward warping): the forward (csrc/splat.hip) scatters 64-bit fixed-point
+    contributions with integer atomics and returns (out, weight); frame, flow, the metric, out and weight are saved, the
+    weight is not differentiable, and the backward (``splat_backward``, csrc/splat_backward.hip) is a pure gather over
+    each source's four taps: no float atomics in either direction, bit-reproducible. Only the gradients
+    ``needs_input_grad`` asks for are formed; the softmax mode's shift by the image's metric maximum counts as a
+    constant. ``splat`` and ``splat_backward`` are listed in ``OPS_SPLAT``, not in ``OPS``.
 """
 from __future__ import annotations
 
@@ -100,6 +106,12 @@ OPS = (
     "batch_norm_act",
     "batch_norm_act_backward",
     "fb_consistency",
+)
+# the forward-warping ops, kept apart from OPS (tests/golden/op_schemas.txt records that tuple as it stood); their
+# schemas are recorded in tests/golden/op_schemas_splat.txt
+OPS_SPLAT = (
+    "splat",
+    "splat_backward",
 )
 _loaded = False
 
@@ -269,6 +281,24 @@ def _alt_backward(ctx, grad_out):
     return (g1.to(d1) if need[0] else None), (g2.to(d2) if need[1] else None), None, [None] * len(f2h), None, None
 
 
+def _splat_setup(ctx, inputs, output):
+    frame, flow, metric, mode = inputs
+    out, weight = output
+    ctx.save_for_backward(frame, flow, metric, out, weight)
+    ctx.mode = mode
+    ctx.mark_non_differentiable(weight)
+
+
+def _splat_backward(ctx, grad_out, _grad_weight):
+    frame, flow, metric, out, weight = ctx.saved_tensors
+    need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]),
+            metric is not None and bool(ctx.needs_input_grad[2])]
+    g_frame, g_flow, g_metric = torch.ops.oflow.splat_backward(grad_out.contiguous(), frame, flow, metric, out, weight,
+                                                               ctx.mode, need)
+    return (g_frame.to(frame.dtype) if need[0] else None), (g_flow.to(flow.dtype) if need[1] else None), \
+        (g_metric.to(metric.dtype) if need[2] else None), None
+
+
 def _register_autograd() -> None:
     ops = torch.ops.oflow
 
@@ -288,3 +318,4 @@ def _register_autograd() -> None:
     reg("oflow::frozen_batch_norm_act", *_param_layer_formula(ops.frozen_batch_norm_act_backward, n_saved=5, n_plain=2))
     reg("oflow::batch_norm_act",
         *_param_layer_formula(ops.batch_norm_act_backward, n_saved=3, n_plain=2, saves_statistics=True))
+    reg("oflow::splat", _splat_setup, _splat_backward)

@@ -127,6 +127,144 @@ def _fb_consistency_torch(a: Tensor, o: Tensor, alpha: float, beta: float) -> Tu
     return mask.unsqueeze(1), err.unsqueeze(1)
 
 
+SPLAT_EPS = _native.SPLAT_EPS
+
+
+def splat(
+    frame: Tensor,
+    flow: Tensor,
+    metric: Optional[Tensor] = None,
+    mode: str = "sum",
+    return_weight: bool = False,
+):
+    """Forward warping (splatting) of a frame along a flow (an addition; the reference has none): summation, average,
+    linear and softmax splatting of Niklaus and Liu (CVPR 2020). Every source pixel (x, y) is pushed to
+    (x + u, y + v) and spread over the four pixels around that point with bilinear weights w;
+    ``N_c(t) = sum w m frame_c`` and ``D(t) = sum w m`` over everything that reaches target t.
+
+    Args:
+        frame: (B, C, H, W)
+        flow: (B, 2, H, W) in **pixel units**, channel 0 = x -- as :func:`fb_consistency` takes it, and not as
+            :func:`warp` does (a normalized flow goes through :func:`denormalize` first)
+        metric: the importance metric (B, 1, H, W) of the "linear" and "soft" modes, else None
+        mode: the per-source weight m --
+            "sum": m = 1, out = N (no normalisation);
+            "avg": m = 1, out = N / (D + EPS);
+            "linear": m = metric (expected >= 0), out = N / (D + EPS);
+            "soft": m = exp(metric - max of metric over that image), out = N / (D + EPS);
+            EPS = 1e-7
+        return_weight: also return D as (B, 1, H, W) fp32, not differentiable; ``D == 0`` marks the holes
+
+    Returns:
+        out (B, C, H, W) fp32, or ``(out, D)``. A pixel that nothing reaches is exactly 0.
+
+    A source whose landing point is non-finite, or has no tap inside the frame, contributes nothing; a tap outside the
+    frame is dropped on its own. "soft" differs from the paper's unshifted form: the shift by the image's maximum keeps
+    exp from overflowing and counts as a constant in the gradient, so EPS acts relative to the image's largest weight,
+    and the returned D is in units of that largest weight. Non-finite frame or metric values make that image's output
+    unspecified (include/oflow.h ``oflow_splat_f32`` states the arithmetic).
+
+    GPU tensors run the native op on the current stream (``torch.ops.oflow.splat``, no host sync): 64-bit fixed-point
+    sums, bit-identical from run to run and independent of the rest of the batch, with a native gather as the backward.
+    CPU tensors run the same arithmetic as a torch composition with ``index_add_`` in float64, differentiable through
+    autograd. Gradients flow to frame, flow and metric.
+    """
+    what = "splat"
+    if mode not in _native.SPLAT_MODES:
+        raise ValueError(f"{what}: unknown mode {mode!r} (one of {sorted(_native.SPLAT_MODES)})")
+    needs_metric = mode in ("linear", "soft")
+    if needs_metric and metric is None:
+        raise ValueError(f"{what}: mode {mode!r} needs a metric")
+    if not needs_metric and metric is not None:
+        raise ValueError(f"{what}: mode {mode!r} takes no metric")
+    for name, t in (("frame", frame), ("flow", flow)) + ((("metric", metric),) if needs_metric else ()):
+        if not isinstance(t, Tensor):
+            raise TypeError(f"{what}: {name} must be a torch.Tensor, got {type(t).__name__}")
+        if not t.is_floating_point():
+            raise TypeError(f"{what}: {name} must be a floating-point tensor, got {t.dtype}")
+    if frame.dim() != 4:
+        raise ValueError(f"{what}: frame must be (B, C, H, W), got {tuple(frame.shape)}")
+    b, _, h, w = frame.shape
+    if tuple(flow.shape) != (b, 2, h, w):
+        raise ValueError(f"{what}: flow must be (B, 2, H, W) = {(b, 2, h, w)}, got {tuple(flow.shape)}")
+    if needs_metric and tuple(metric.shape) != (b, 1, h, w):
+        raise ValueError(f"{what}: metric must be (B, 1, H, W) = {(b, 1, h, w)}, got {tuple(metric.shape)}")
+    if flow.device != frame.device or (needs_metric and metric.device != frame.device):
+        raise ValueError(f"{what}: all tensors must be on one device")
+    if frame.is_cuda:
+        out, weight = _native.splat(frame, flow, metric, mode)
+    else:
+        out, weight = _splat_torch(frame.float(), flow.float(), metric.float() if needs_metric else None, mode)
+    return (out, weight) if return_weight else out
+
+
+def _splat_torch(frame: Tensor, flow: Tensor, metric: Optional[Tensor], mode: str) -> Tuple[Tensor, Tensor]:
+    """``splat`` on fp32 CPU tensors in plain torch: the contract of include/oflow.h with the sums taken in float64 by
+    ``index_add_`` instead of in fixed point (the same values to within the fixed-point quantum), differentiable."""
+    b, c, h, w = frame.shape
+    hw = h * w
+    if frame.numel() == 0 or hw == 0:
+        return frame.new_zeros((b, c, h, w)), frame.new_zeros((b, 1, h, w))
+    px = torch.arange(w, dtype=torch.float32).view(1, 1, w) + flow[:, 0]  # fp32 sums, rounded once
+    py = torch.arange(h, dtype=torch.float32).view(1, h, 1) + flow[:, 1]
+    keep = (px > -1) & (px < w) & (py > -1) & (py < h)  # False for NaN
+    pxs, pys = torch.where(keep, px, 0.0), torch.where(keep, py, 0.0)
+    x0f, y0f = torch.floor(pxs.detach()), torch.floor(pys.detach())
+    fx, fy = pxs.double() - x0f.double(), pys.double() - y0f.double()  # exact in float64
+    x0, y0 = x0f.long(), y0f.long()
+    if mode == "linear":
+        m = metric[:, 0].double()
+    elif mode == "soft":
+        m = torch.exp(metric[:, 0] - metric.detach().reshape(b, -1).amax(dim=1).view(b, 1, 1)).double()
+    else:
+        m = torch.ones((b, h, w), dtype=torch.float64)
+    f64 = frame.double().permute(1, 0, 2, 3).reshape(c, b * hw)
+    num = torch.zeros((c, b * hw), dtype=torch.float64)
+    den = torch.zeros(b * hw, dtype=torch.float64)
+    base = (torch.arange(b) * hw).view(b, 1, 1)
+    for dy in (0, 1):
+        for dx in (0, 1):
+            x, y = x0 + dx, y0 + dy
+            ok = keep & (x >= 0) & (x < w) & (y >= 0) & (y < h)
+            wm = ((fx if dx else 1.0 - fx) * (fy if dy else 1.0 - fy)) * m
+            wm = torch.where(ok, wm, torch.zeros_like(wm)).reshape(-1)  # a dropped tap adds 0 to pixel 0
+            idx = (torch.where(ok, y * w + x, torch.zeros_like(x)) + base).reshape(-1)
+            den = den.index_add(0, idx, wm)
+            num = num.index_add(1, idx, wm * f64)
+    out = num if mode == "sum" else num / (den + SPLAT_EPS)
+    out = out.view(c, b, h, w).permute(1, 0, 2, 3).contiguous()
+    return out.float(), den.detach().view(b, 1, h, w).float()
+
+
+def interpolate_frame(
+    frame0: Tensor,
+    frame1: Tensor,
+    flow_fw: Tensor,
+    flow_bw: Tensor,
+    t: float = 0.5,
+    metric0: Optional[Tensor] = None,
+    metric1: Optional[Tensor] = None,
+) -> Tensor:
+    """The frame at time t in [0, 1] between ``frame0`` (t = 0) and ``frame1`` (t = 1) by forward warping both:
+    ``frame0`` is splatted along ``t * flow_fw`` and ``frame1`` along ``(1 - t) * flow_bw`` (flows in pixel units, as
+    :func:`splat` takes them), "soft" with the metrics when both are given, else "avg", and the two are blended by
+    their distance in time over the pixels each one reaches:
+    ``((1 - t) h0 s0 + t h1 s1) / ((1 - t) h0 + t h1)`` with ``h = (D > 0)``; 0 where both have a hole.
+
+    The usual metric is photometric consistency,
+    ``metric0 = -alpha * (frame0 - warp(frame1, normalize(flow_fw))).abs().mean(1, keepdim=True)`` (and the mirror
+    image for ``metric1``); ``alpha`` is the caller's to choose -- nothing here has tuned it.
+    """
+    if (metric0 is None) != (metric1 is None):
+        raise ValueError("interpolate_frame: give both metrics or neither")
+    mode = "avg" if metric0 is None else "soft"
+    s0, d0 = splat(frame0, flow_fw * t, metric0, mode, return_weight=True)
+    s1, d1 = splat(frame1, flow_bw * (1.0 - t), metric1, mode, return_weight=True)
+    a0, a1 = (1.0 - t) * (d0 > 0).to(s0.dtype), t * (d1 > 0).to(s1.dtype)
+    total = a0 + a1
+    return (a0 * s0 + a1 * s1) / torch.where(total > 0, total, torch.ones_like(total))
+
+
 def warp_grid(flow: Tensor) -> Tensor:
     """Sampling grid (B, H, W, 2) = linspace(-1, 1) base grid + normalized flow (B, H, W, 2)
     (`operator.py:36-56`). ``warp`` does not call this: its kernel forms the same grid in registers."""
