@@ -48,14 +48,8 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--layer", default=None, help="only layers whose name contains this string (PMC runs)")
     ap.add_argument("--no-lookup", action="store_true")
-    ap.add_argument("--ablate", action="store_true", help="with the -DOFLOW_ABLATE library build (OFLOW_LIB): per-layer "
-                    "times with kernel parts dropped (exp_flags: 2 MFMAs, 4 A staging, 16 epilogue, 32 B staging, "
-                    "64 main-loop barriers)")
     ap.add_argument("--shape-batch", type=int, default=0, help="override the batch (pairs) of --shape")
-    ap.add_argument("--conv-flags", type=int, default=0, help="oflow_exp_set_conv_flags value for the run (experiments)")
     args = ap.parse_args()
-    if args.conv_flags:
-        N.load().oflow_exp_set_conv_flags(args.conv_flags)
     b, h, w = SHAPES[args.shape]
     if args.shape_batch:
         b = args.shape_batch
@@ -105,13 +99,6 @@ def main():
             kw_ = dict(f32=torch.zeros(b, 2, h, w, device=dev), f32_accumulate=True)
         ms = timed(lambda: N.conv_s32(N.S32Slice(x), cw, bn, **kw_), args.iters)
         total += ms
-        if args.ablate:  # the -DOFLOW_ABLATE library: time with parts of the kernel dropped
-            lib = N.load()
-            abl = {}
-            for f in (2, 4, 16, 32, 64, 2 | 4 | 32, 2 | 4 | 16 | 32 | 64):
-                lib.oflow_exp_set_conv_flags(f)
-                abl[str(f)] = round(timed(lambda: N.conv_s32(N.S32Slice(x), cw, bn, **kw_), args.iters) * 1e3, 1)
-            lib.oflow_exp_set_conv_flags(0)
         flops = 2.0 * P * n * cin * kh * kw
         padded = 2.0 * P * npad * (gi * 32) * kh * kw * 3
         out["layers"][name] = {
@@ -119,8 +106,6 @@ def main():
             "tflops_f32_equiv": round(flops / ms / 1e9, 1),
             "mfma_frac": round(padded / (ms * 1e-3) / F16_PEAK, 3),
         }
-        if args.ablate:
-            out["layers"][name]["ablated_us"] = abl
     out["update_iteration_convs_us"] = round(total * 1e3, 1)
     if args.no_lookup:
         print(json.dumps(out, indent=1))

@@ -18,8 +18,8 @@
 // Workgroup tile: 4 output rows x 32 output columns (128 pixels) x BN output channels; 4 waves as WM x WN.
 // Loop: input groups (k32) outer, taps inner. Per group the (4 + KH - 1) x (32 + KW - 1) input halo is staged in
 // LDS once and read by every tap at a shifted offset; per (group, tap) a BN x 128-B weight slab is staged (double
-// buffered). Both are register-staged (B one step, the halo one group ahead). LDS lines are 16-B-slot swizzled
-// (slot ^= (row >> 1) & 7) so that the 32 rows of an MFMA operand read by ds_read_b128 are bank-conflict free.
+// buffered). Both are register-staged (B one step, the halo one group ahead). LDS operand rows are padded to 144 B
+// so that the 32 rows of an MFMA operand read by ds_read_b128 are bank-conflict free.
 // Epilogue: accumulators -> LDS tile [pixel][channel] fp32 -> per-channel scale, bias, activation and the fused
 // consumer (S32 stores with 16-B chunks, GRU gates, fp32 NCHW store/accumulate).
 #include "oflow_internal.h"
@@ -31,48 +31,8 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));  // native vector: stays in VGPRs (HIP uint4 is copied by memcpy)
 
-__device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
-// operand rows in LDS: 144-B padded rows (1) or 128-B rows with XOR-swizzled 16-B slots (0; build with
-// VECFLAGS+=-DOFLOW_PAD_ROWS=0 for A/B). Both are conflict-free for the ds_read_b128 operand reads; the padded rows
-// make every read address one per-lane base plus an immediate (no per-read swizzle arithmetic).
-// register-direct weights: steps of B fragments in flight (2 or 3: measured neutral, profiles/r04/s18_*; default 2)
-#ifndef OFLOW_BREG_RING
-#define OFLOW_BREG_RING 2
-#endif
-// register-direct weights, vertical taps: halo-row operands reused across taps (1; 0 = re-read per tap, for A/B)
-#ifndef OFLOW_VSLIDE
-#define OFLOW_VSLIDE 1
-#endif
-// XCD-aware workgroup order (1) or the 2D grid (tile, channel block) (0, default): measured no faster -- per layer
-// alone 977.9 (2D) vs 986.8 us per update iteration, benches 422.0 / 423.4 vs 421.2 / 420.7 pairs/s alternated on one
-// box (profiles/r04/s21_*): the halo re-reads of a tile's second channel block already hit the Infinity Cache
-#ifndef OFLOW_XCD_MAP
-#define OFLOW_XCD_MAP 0
-#endif
-#ifndef OFLOW_STEM_SINGLE_A
-#define OFLOW_STEM_SINGLE_A 1
-#endif
-#ifndef OFLOW_PAD_ROWS
-#define OFLOW_PAD_ROWS 1
-#endif
-// register-direct weights: the halo double-buffered in LDS (1): group g+1's halo is written into the buffer group g-1
-// used while group g's MFMAs run, one barrier per group instead of two around a single buffer's swap. Bit-identical,
-// but the step is 0.1-0.3 ms slower (the doubled halo, up to 74 KB per workgroup, crowds the other lane's workgroups
-// off the CUs: profiles/r05/s25_step_ab.log), so the single buffer (0) stays the default.
-#ifndef OFLOW_HALO_DB
-#define OFLOW_HALO_DB 0
-#endif
-
 constexpr int kTY = 4, kTX = 32;  // default tile: kTY rows x kTX columns
 
-// ablation build (tools/exp: -DOFLOW_ABLATE): exp_flags bits drop parts of the kernel to time the rest (2 MFMAs, 4 A
-// staging writes, 8 instance-norm partials, 16 epilogue stores, 32 B staging writes, 64 the main loop's per-step
-// barrier); the product build compiles every test to false
-#ifdef OFLOW_ABLATE
-#define OFLOW_ABL(bit) ((a.exp_flags & (bit)) != 0)
-#else
-#define OFLOW_ABL(bit) false
-#endif
 constexpr int kAinGroups = 4;                      // AIN inputs: up to 128 channels (the encoders' 64 / 96 / 128)
 
 
@@ -119,7 +79,7 @@ struct ConvArgs {
   int cin;                 // kInF32: real input channels (row pitch cin * 4 B); channels >= cin stage as zeros
   int wbytes;              // bytes of the packed weights (kg * taps * npad * 128)
   const uint8_t* wf;       // the same weights fragment-major (register-direct B, BREG kernels), or null
-  int exp_flags;           // experiments only (oflow_exp_set_conv_flags): bit 0 = the stem's element-wise window loop
+  int exp_flags;           // oflow_exp_set_conv_flags: bit 256 = libm gates (the only bit left; the GRU tests run both)
   // flow-head epilogue (EPI 3, OFLOW_EPI_FLOW_HEAD): the output conv's weights [slab][64][18] and the per-tap partial
   // sums [slabs][B][18][H][W] (fp32)
   const float* fhw;
@@ -290,7 +250,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
   // T == 1 (1x1 convs): the input tile changes every K-step, so A is staged like B (double buffered in LDS).
   // The stem (kInImg) builds A from the image window already in LDS, so nothing is gained by building A(i+1) beside
   // A(i): one A buffer and the halo-swap schedule (a barrier before each rebuild) -- 50.5 instead of 68.9 KB of LDS,
-  // three workgroups per CU instead of two (OFLOW_STEM_SINGLE_A=0: the double buffer, for A/B).
+  // three workgroups per CU instead of two.
   // input windows (the stem's image, convf1's flow): the patch operand is built per tile from a window staged in LDS
   constexpr bool WIN = AIN == kInImg || AIN == kInFlow;
   constexpr int WC = AIN == kInFlow ? 2 : kImgC, WS = AIN == kInFlow ? 1 : 2;  // window channels, stride
@@ -302,20 +262,15 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
   constexpr int WAPER = WIN ? BM * 4 / NTH : 1;      // window input: (pixel, 8 patch channels) items per thread
   static_assert(!WIN || (BM * 4) % NTH == 0, "window items");
   static_assert(AIN != kInImg || (WHALF == kImgHalf && WPITCH == kImgPitch && WPLANE == kImgPlane), "stem window");
-  constexpr bool ADB = (T == 1) && !(WIN && OFLOW_STEM_SINGLE_A);
-  // 128-B LDS rows, 16-B slots XOR-swizzled (slot ^= (row >> 1) & 7): the 32 rows of an MFMA operand read by
-  // ds_read_b128 are bank-conflict free from any starting row (padded 144-B rows with affine addressing measured the
-  // same speed, tools/exp/conv_s32_dma.hip's history)
-  constexpr int RS = 128;
-  // BREG: the halo rows padded to 144 B instead of swizzled (consecutive rows start 36 banks apart: the 16 rows of a
-  // ds_read_b128 phase are conflict-free), so every A read is one per-lane base plus an immediate offset (the swizzle
-  // costs ~4 VALU per read, 16 reads per step with 4 row tiles per wave)
-  constexpr int RSA = (BREG || OFLOW_PAD_ROWS) ? 144 : RS, RSB = OFLOW_PAD_ROWS ? 144 : RS;
+  constexpr bool ADB = (T == 1) && !WIN;
+  // LDS operand rows (128 B of data) padded to 144 B: consecutive rows start 36 banks apart, so the 16 rows of a
+  // ds_read_b128 phase are conflict-free, and every operand read is one per-lane base plus an immediate offset (the
+  // XOR slot swizzle that 128-B rows need costs ~4 VALU per read: DESIGN.md §4 conv_s32)
+  constexpr int RSA = 144, RSB = 144;
   constexpr int A_BYTES = NPIX * RSA, B_BYTES = BN * RSB;
   static_assert(!BREG || (T > 1 && (WM == 1 || WM == 2 || WM == 4) && BN == 32 * WN && AIN == kInS32),
                 "register-direct B: T > 1, WM x WN waves of one 32-channel tile each");
-  constexpr bool HDB = BREG && OFLOW_HALO_DB;  // double-buffered halo (register-direct kernels)
-  constexpr int MAIN_BYTES = ((ADB || HDB) ? 2 : 1) * A_BYTES + (BREG ? 0 : 2 * B_BYTES);
+  constexpr int MAIN_BYTES = (ADB ? 2 : 1) * A_BYTES + (BREG ? 0 : 2 * B_BYTES);
   constexpr int TS = BN + 4;              // epilogue tile row stride (floats)
   constexpr int EPI_BYTES = BM * TS * 4;
   constexpr int LDS_BYTES = MAIN_BYTES > EPI_BYTES ? MAIN_BYTES : EPI_BYTES;
@@ -341,30 +296,10 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   const int r = lane & 31, hh = lane >> 5;
-  auto aswz = [](int p) { return (BREG || OFLOW_PAD_ROWS) ? 0 : swz(p); };  // row slot swizzles (none with padded rows)
-  auto bswz = [](int n) { return OFLOW_PAD_ROWS ? 0 : swz(n); };
 
-  // workgroup -> (tile, channel block). XCD-aware (OFLOW_XCD_MAP): workgroups are dealt round-robin over the 8 XCDs
-  // (each with its own L2), so ids 8 apart share one; the channel blocks of a tile take ids 8 apart within a group of
-  // 8 * nblk ids and run on one XCD close together in time -- the second reads the tile's halo from that L2 instead of
-  // from the fabric (a 2D grid runs every tile's block 0 before any block 1)
-  int tile, cblk;
-  if constexpr (OFLOW_XCD_MAP) {
-    const int nblk = a.npad / BN, ntiles = a.tiles_x * a.tiles_y * a.B, bid = blockIdx.x;
-    const int full = (ntiles >> 3) * 8 * nblk;
-    if (bid < full) {
-      const int grp = bid / (8 * nblk), rem = bid - grp * 8 * nblk;
-      cblk = rem >> 3;
-      tile = grp * 8 + (rem & 7);
-    } else {
-      const int ntail = ntiles & 7, rem = bid - full;
-      cblk = rem / ntail;
-      tile = (ntiles & ~7) + (rem - cblk * ntail);
-    }
-  } else {
-    tile = blockIdx.x;
-    cblk = blockIdx.y;
-  }
+  // workgroup -> (tile, channel block): the 2D grid of conv_grid
+  int tile = blockIdx.x;
+  const int cblk = blockIdx.y;
   const int tx0 = (tile % a.tiles_x) * kTX;
   tile /= a.tiles_x;
   const int ty0 = (tile % a.tiles_y) * TY;
@@ -375,7 +310,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
   // Register staging: one register set per operand; B(i+1) is written to LDS at step i's start and the set reloaded
   // with B(i+2) right after. A (one group's halo) is loaded at the group's first tap and written at its last; for 1x1
   // convs A follows B's scheme.
-  u32x4 ra[APER], rb[BPER];
+  u32x4 ra[APER];
   // Global loads are raw buffer loads: a per-lane 32-bit offset (fixed for the whole loop) plus the step's uniform
   // byte offset in an SGPR, so the loop spends no vector instructions on addresses. Every load is unconditional (no
   // exec branches), so the compiler counts vmcnt precisely: halo pixels outside the image load a clamped in-image
@@ -410,18 +345,17 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
 #pragma unroll
   for (int s_ = 0; s_ < BPER; ++s_) boff[s_] = (n0 + (tid + s_ * NTH) / 8) * 128 + ((tid + s_ * NTH) & 7) * 16;
 #define OFLOW_LOAD_A(RA, G)                                                                                          \
-  if constexpr (!WIN) _Pragma("unroll") for (int s_ = 0; s_ < APER; ++s_) {                                        \
+  if constexpr (!WIN) _Pragma("unroll") for (int s_ = 0; s_ < APER; ++s_) {                                          \
     int col_;                                                                                                        \
     const int off_ = a_off(s_, col_);                                                                                \
-    if constexpr (AIN == kInF32) /* rows of cin floats: channels past cin re-read the row's last 16 B (zeroed) */   \
-      RA[s_] = __builtin_amdgcn_raw_buffer_load_b128(rsA, off_ + min((G) * 128 + col_, a.cin * 4 - 16), 0, 0);      \
+    if constexpr (AIN == kInF32) /* rows of cin floats: channels past cin re-read the row's last 16 B (zeroed) */    \
+      RA[s_] = __builtin_amdgcn_raw_buffer_load_b128(rsA, off_ + min((G) * 128 + col_, a.cin * 4 - 16), 0, 0);       \
     else                                                                                                             \
-      RA[s_] = __builtin_amdgcn_raw_buffer_load_b128(rsA, off_, (G) * 128, 0);                                      \
+      RA[s_] = __builtin_amdgcn_raw_buffer_load_b128(rsA, off_, (G) * 128, 0);                                       \
   }
 // (one range-guard branch per call: the max |x| of all the thread's split values; the normalising affine of the
 // thread's 4 channels read once: an item's chunk is tid & 7 for every item, NTH being a multiple of 8)
 #define OFLOW_WRITE_A(RA, BUF, G)                                                                                    \
-  if (!OFLOW_ABL(4)) {                                                                                               \
   float amx_ = 0.f;                                                                                                  \
   float2 af4_[4];                                                                                                    \
   if constexpr (AIN == kInF32Norm) _Pragma("unroll") for (int e_ = 0; e_ < 4; ++e_)                                  \
@@ -446,15 +380,15 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
       half8 h8_, l8_;                                                                                                \
       split_vec(v8_, h8_, l8_);                                                                                      \
       uint8_t* rw_ = sA + (BUF) * A_BYTES + p * RSA;                                                                 \
-      *reinterpret_cast<half8*>(rw_ + ((cp ^ aswz(p)) << 4)) = h8_;                                                  \
-      *reinterpret_cast<half8*>(rw_ + (((4 + cp) ^ aswz(p)) << 4)) = l8_;                                            \
+      *reinterpret_cast<half8*>(rw_ + (cp << 4)) = h8_;                                                              \
+      *reinterpret_cast<half8*>(rw_ + ((4 + cp) << 4)) = l8_;                                                        \
     }                                                                                                                \
   } else                                                                                                             \
   _Pragma("unroll") for (int s_ = 0; s_ < APER; ++s_) {                                                              \
-    const int item = tid + s_ * NTH;                                                                            \
+    const int item = tid + s_ * NTH;                                                                                 \
     /* the 8 chunks of a pixel (whole 128-B LDS rows per 8 lanes) */                                                 \
     const int p = item >> 3, c = item & 7;                                                                           \
-    if (AITEMS % NTH == 0 || item < AITEMS) {                                                                   \
+    if (AITEMS % NTH == 0 || item < AITEMS) {                                                                        \
       if constexpr (AIN != kInS32) {                                                                                 \
         /* 4 fp32 channels (G*32 + 4c ..) [-> relu(x * scale + shift)] -> 4 hi + 4 lo halves (8 B each) */           \
         typedef _Float16 half4_ __attribute__((ext_vector_type(4)));                                                 \
@@ -476,54 +410,53 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
           amx_ = fmaxf(amx_, mx_);                                                                                   \
         }                                                                                                            \
         uint8_t* rw_ = sA + (BUF) * A_BYTES + p * RSA + (c & 1) * 8;                                                 \
-        *reinterpret_cast<half4_*>(rw_ + (((c >> 1) ^ aswz(p)) << 4)) = h4;                                          \
-        *reinterpret_cast<half4_*>(rw_ + (((4 + (c >> 1)) ^ aswz(p)) << 4)) = l4;                                    \
+        *reinterpret_cast<half4_*>(rw_ + ((c >> 1) << 4)) = h4;                                                      \
+        *reinterpret_cast<half4_*>(rw_ + ((4 + (c >> 1)) << 4)) = l4;                                                \
       } else {                                                                                                       \
-        *reinterpret_cast<u32x4*>(sA + (BUF) * A_BYTES + p * RSA + ((c ^ aswz(p)) << 4)) =                          \
+        *reinterpret_cast<u32x4*>(sA + (BUF) * A_BYTES + p * RSA + (c << 4)) =                                       \
             ((aok >> s_) & 1u) ? RA[s_] : u32x4{0u, 0u, 0u, 0u};                                                     \
       }                                                                                                              \
     }                                                                                                                \
   }                                                                                                                  \
-  if constexpr (AIN != kInS32) range_guard(amx_);                                                                    \
-  }
+  if constexpr (AIN != kInS32) range_guard(amx_);
 #define OFLOW_LOAD_B(RB, STEP)                                                                                       \
   _Pragma("unroll") for (int s_ = 0; s_ < BPER; ++s_) {                                                              \
-    const int item = tid + s_ * NTH;                                                                            \
-    if (BITEMS % NTH == 0 || item < BITEMS)                                                                     \
-      RB[s_] = __builtin_amdgcn_raw_buffer_load_b128(rsB, boff[s_], (STEP) * a.npad * 128, 0);                      \
+    const int item = tid + s_ * NTH;                                                                                 \
+    if (BITEMS % NTH == 0 || item < BITEMS)                                                                          \
+      RB[s_] = __builtin_amdgcn_raw_buffer_load_b128(rsB, boff[s_], (STEP) * a.npad * 128, 0);                       \
   }
 #define OFLOW_WRITE_B(RB, BUF)                                                                                       \
-  if (!OFLOW_ABL(32)) _Pragma("unroll") for (int s_ = 0; s_ < BPER; ++s_) {                                          \
-    const int item = tid + s_ * NTH;                                                                            \
+  _Pragma("unroll") for (int s_ = 0; s_ < BPER; ++s_) {                                                              \
+    const int item = tid + s_ * NTH;                                                                                 \
     const int n = item >> 3, c = item & 7;                                                                           \
-    if (BITEMS % NTH == 0 || item < BITEMS)                                                                     \
-      *reinterpret_cast<u32x4*>(sB + (BUF) * B_BYTES + n * RSB + ((c ^ bswz(n)) << 4)) = RB[s_];                    \
+    if (BITEMS % NTH == 0 || item < BITEMS)                                                                          \
+      *reinterpret_cast<u32x4*>(sB + (BUF) * B_BYTES + n * RSB + (c << 4)) = RB[s_];                                 \
   }
   // operands of one 16-deep sub-step S_ of step I: A rows of this wave's pixel tiles at the step's tap offset, B rows
   // of its channel tiles; hi and lo halves
 #define OFLOW_READ_OPS(AH, AL, BH, BL, I, S_)                                                                        \
   {                                                                                                                  \
-    const int ii_ = (I);                                                                                              \
-    const int t_ = ii_ % T, ky_ = t_ / KW, kx_ = t_ - ky_ * KW;                                                       \
-    const uint8_t* bufA_ = sA + (ADB ? (ii_ & 1) * A_BYTES : 0);                                                      \
-    const uint8_t* bufB_ = sB + (ii_ & 1) * B_BYTES;                                                                  \
+    const int ii_ = (I);                                                                                             \
+    const int t_ = ii_ % T, ky_ = t_ / KW, kx_ = t_ - ky_ * KW;                                                      \
+    const uint8_t* bufA_ = sA + (ADB ? (ii_ & 1) * A_BYTES : 0);                                                     \
+    const uint8_t* bufB_ = sB + (ii_ & 1) * B_BYTES;                                                                 \
     const int chi_ = 2 * (S_) + hh, clo_ = 4 + 2 * (S_) + hh;                                                        \
     _Pragma("unroll") for (int mt_ = 0; mt_ < MT; ++mt_) {                                                           \
       const int p_ = (wm * MT + mt_ + ky_) * HX + r + kx_;                                                           \
       const uint8_t* row_ = bufA_ + p_ * RSA;                                                                        \
-      AH[mt_] = *reinterpret_cast<const half8*>(row_ + ((chi_ ^ aswz(p_)) << 4));                                    \
-      AL[mt_] = *reinterpret_cast<const half8*>(row_ + ((clo_ ^ aswz(p_)) << 4));                                    \
+      AH[mt_] = *reinterpret_cast<const half8*>(row_ + (chi_ << 4));                                                 \
+      AL[mt_] = *reinterpret_cast<const half8*>(row_ + (clo_ << 4));                                                 \
     }                                                                                                                \
     _Pragma("unroll") for (int nt_ = 0; nt_ < NT; ++nt_) {                                                           \
       const int n_ = wn * (BN / WN) + nt_ * 32 + r;                                                                  \
       const uint8_t* row_ = bufB_ + n_ * RSB;                                                                        \
-      BH[nt_] = *reinterpret_cast<const half8*>(row_ + ((chi_ ^ bswz(n_)) << 4));                                    \
-      BL[nt_] = *reinterpret_cast<const half8*>(row_ + ((clo_ ^ bswz(n_)) << 4));                                    \
+      BH[nt_] = *reinterpret_cast<const half8*>(row_ + (chi_ << 4));                                                 \
+      BL[nt_] = *reinterpret_cast<const half8*>(row_ + (clo_ << 4));                                                 \
     }                                                                                                                \
   }
   // hi*lo + lo*hi + hi*hi per (pixel tile, channel tile): the lo*lo term is below fp32 rounding
 #define OFLOW_MFMAS(AH, AL, BH, BL)                                                                                  \
-  if (!OFLOW_ABL(2)) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                               \
+  _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                                  \
     _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) {                                                              \
       acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH[mt], BL[nt], acc[mt][nt], 0, 0, 0);                    \
       acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL[mt], BH[nt], acc[mt][nt], 0, 0, 0);                    \
@@ -555,17 +488,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
     // every load of the window issued before the first LDS store (clamped in-image addresses, zero selected after):
     // a load -> store loop waited out one memory round trip per element (the stem ran 0.6 ms per 8 images)
     constexpr int IMG_N = kImgC * kImgRows * kImgCols, IMG_PER = (IMG_N + NTH - 1) / NTH;
-    if (a.exp_flags & 1) {  // experiment: the element-wise load -> store loop
-      for (int e = tid; e < IMG_N; e += NTH) {
-        const int ch = e / (kImgRows * kImgCols), rem = e - ch * (kImgRows * kImgCols);
-        const int ry = rem / kImgCols, rx = rem - ry * kImgCols;
-        const int iy = iy0 + ry, ix = ix0 + rx;
-        float v = 0.f;
-        if (static_cast<unsigned>(iy) < static_cast<unsigned>(2 * a.H) && static_cast<unsigned>(ix) < static_cast<unsigned>(2 * a.W))
-          v = img[((long long)ch * (2 * a.H) + iy) * (2 * a.W) + ix];
-        sImg[ch * kImgPlane + ry * kImgPitch + (rx & 1) * kImgHalf + (rx >> 1)] = v;
-      }
-    } else {
     float iv[IMG_PER];
     int io[IMG_PER];
 #pragma unroll
@@ -583,7 +505,6 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
 #pragma unroll
     for (int s_ = 0; s_ < IMG_PER; ++s_)
       if (tid + s_ * NTH < IMG_N) sImg[io[s_]] = iv[s_];
-    }
   }
   if constexpr (AIN == kInFlow) {
     // convf1's input: the tile's flow window (rows ty0 - 3 .., columns tx0 - 3 ..) from coords1 (B, 2, H, W):
@@ -630,29 +551,29 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
   const int wstep = a.npad * 128;  // bytes per (group, tap) step
   // ring of RING steps' B fragments: step i in bq[i % RING]; [sub-step * 2 + (hi, lo)]. Vector-memory loads retire in
   // issue order, so the loads of B issued after a group's halo prefetch (HBM latency) cannot be consumed before it:
-  // the ring depth is how many steps the prefetch has before a B wait covers it. 3 where the registers allow it.
-  constexpr int RING = (T == 5 && KH == 5 && EPI == 0) ? 2 : OFLOW_BREG_RING;  // (the 5x1 context conv: 255 VGPRs at 2)
+  // the ring depth is how many steps the prefetch has before a B wait covers it (a ring of 3 measured neutral where
+  // the registers allow it, and the 5x1 context conv is at 255 VGPRs with 2: DESIGN.md §4 conv_s32).
+  constexpr int RING = 2;
   u32x4 bq[RING][4];
   auto load_b = [&](u32x4 (&d)[4], int step) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) d[e] = __builtin_amdgcn_raw_buffer_load_b128(rsW, wlane + e * 1024, step * wstep, 0);
   };
-#define OFLOW_READ_A(AH, AL, I, S_)                                                                                   \
+#define OFLOW_READ_A(AH, AL, I, S_)                                                                                  \
   {                                                                                                                  \
-    const int ii_ = (I);                                                                                              \
-    const int t_ = ii_ % T, ky_ = t_ / KW, kx_ = t_ - ky_ * KW;                                                       \
+    const int ii_ = (I);                                                                                             \
+    const int t_ = ii_ % T, ky_ = t_ / KW, kx_ = t_ - ky_ * KW;                                                      \
     const int chi_ = 2 * (S_) + hh, clo_ = 4 + 2 * (S_) + hh;                                                        \
-    const uint8_t* sAb_ = sA + (HDB && ((ii_ / T) & 1) ? A_BYTES : 0); /* group (I / T)'s halo buffer */          \
     _Pragma("unroll") for (int mt_ = 0; mt_ < MT; ++mt_) {                                                           \
       const int p_ = (wm * MT + mt_ + ky_) * HX + r + kx_;                                                           \
-      const uint8_t* row_ = sAb_ + p_ * RSA;                                                                         \
+      const uint8_t* row_ = sA + p_ * RSA;                                                                           \
       AH[mt_] = *reinterpret_cast<const half8*>(row_ + (chi_ << 4));                                                 \
       AL[mt_] = *reinterpret_cast<const half8*>(row_ + (clo_ << 4));                                                 \
     }                                                                                                                \
   }
-#define OFLOW_MFMAS_R(AH, AL, BC, S_)                                                                                 \
-  if (!OFLOW_ABL(2)) _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) {                                             \
-    const half8 bh_ = __builtin_bit_cast(half8, BC[2 * (S_)]), bl_ = __builtin_bit_cast(half8, BC[2 * (S_) + 1]);     \
+#define OFLOW_MFMAS_R(AH, AL, BC, S_)                                                                                \
+  _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) {                                                                \
+    const half8 bh_ = __builtin_bit_cast(half8, BC[2 * (S_)]), bl_ = __builtin_bit_cast(half8, BC[2 * (S_) + 1]);    \
     acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH[mt], bl_, acc[mt][0], 0, 0, 0);                           \
     acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL[mt], bh_, acc[mt][0], 0, 0, 0);                           \
     acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH[mt], bh_, acc[mt][0], 0, 0, 0);                           \
@@ -664,21 +585,20 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
   OFLOW_LOAD_A(ra, a.kg > 1 ? 1 : 0);
   __syncthreads();
   // a loop body of a multiple of RING steps keeps the ring slot of every step static: GPB groups per body
-  constexpr int GPB = (T % RING == 0) ? 1 : RING;  // (RING 2 or 3, both prime)
+  constexpr int GPB = (T % RING == 0) ? 1 : RING;  // (an odd T: two groups per body)
   // Vertical taps (KH x 1): tap ky of row tile mt reads halo row mt + ky, so consecutive taps share MT - 1 of their MT
   // rows: the operands live in registers per halo row and each step reads only its newest row (one row tile's 4 reads
   // instead of MT's 16; LDS operand reads were ~30 of a GRU conv's ~145 us, profiles/r04/s18_abl.log).
-  constexpr bool VSLIDE = OFLOW_VSLIDE && KW == 1 && KH > 1 && WM == 1 && !(EPI == 0 && KH == 5);  // (5x1 EPI 0: VGPRs)
+  constexpr bool VSLIDE = KW == 1 && KH > 1 && WM == 1 && !(EPI == 0 && KH == 5);  // (5x1 EPI 0: VGPRs)
   if constexpr (VSLIDE) {
     constexpr int NR = MT + KH - 1;  // halo rows per group
     half8 V[NR][2][2];               // [halo row][sub-step][hi, lo]
-    auto rd = [&](int hr, int sub, int grp) {
-      const uint8_t* row_ = sA + (HDB && (grp & 1) ? A_BYTES : 0) + (hr * HX + r) * RSA;
+    auto rd = [&](int hr, int sub) {
+      const uint8_t* row_ = sA + (hr * HX + r) * RSA;
       V[hr][sub][0] = *reinterpret_cast<const half8*>(row_ + ((2 * sub + hh) << 4));
       V[hr][sub][1] = *reinterpret_cast<const half8*>(row_ + ((4 + 2 * sub + hh) << 4));
     };
     auto mf = [&](int ky, int sub, u32x4 (&bc)[4]) {
-      if (OFLOW_ABL(2)) return;
       const half8 bh_ = __builtin_bit_cast(half8, bc[2 * sub]), bl_ = __builtin_bit_cast(half8, bc[2 * sub + 1]);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
@@ -688,7 +608,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
       }
     };
 #pragma unroll
-    for (int m = 0; m < MT; ++m) rd(m, 0, 0);
+    for (int m = 0; m < MT; ++m) rd(m, 0);
     for (int g0 = 0; g0 < a.kg; g0 += GPB) {
 #pragma unroll
       for (int j = 0; j < GPB * T; ++j) {
@@ -698,26 +618,21 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
         u32x4 (&bc)[4] = bq[j % RING];
         if (t == 0) {
 #pragma unroll
-          for (int m = 0; m < MT; ++m) rd(m, 1, gg);
+          for (int m = 0; m < MT; ++m) rd(m, 1);
         } else {
-          rd(t + MT - 1, 1, gg);
+          rd(t + MT - 1, 1);
         }
         mf(t, 0, bc);
         if (t == T - 1) {
-          if constexpr (HDB) {
-            // group gg+1's halo into the other buffer (last read in group gg-1, before the previous barrier)
-            OFLOW_WRITE_A(ra, (gg + 1) & 1, gg + 1 < a.kg ? gg + 1 : gg);
-          } else {
-            __syncthreads();
-            OFLOW_WRITE_A(ra, 0, gg + 1 < a.kg ? gg + 1 : gg);
-          }
+          __syncthreads();
+          OFLOW_WRITE_A(ra, 0, gg + 1 < a.kg ? gg + 1 : gg);
           const int g2 = gg + 2 < a.kg ? gg + 2 : a.kg - 1;
           OFLOW_LOAD_A(ra, g2);
           __syncthreads();
 #pragma unroll
-          for (int m = 0; m < MT; ++m) rd(m, 0, gg + 1);  // the next group's first tap (rows 0 .. MT-1: free since tap MT-1)
+          for (int m = 0; m < MT; ++m) rd(m, 0);  // the next group's first tap (rows 0 .. MT-1: free since tap MT-1)
         } else {
-          rd(t + MT, 0, gg);  // the next tap's new row
+          rd(t + MT, 0);  // the next tap's new row
         }
         mf(t, 1, bc);
         load_b(bc, i_ + RING < S ? i_ + RING : S - 1);
@@ -736,12 +651,8 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
       OFLOW_READ_A(yah, yal, i_, 1);
       OFLOW_MFMAS_R(xah, xal, bc, 0);
       if (t == T - 1) {  // the halo swap: every wave done reading A(g); A(g+1) visible before its first read
-        if constexpr (HDB) {
-          OFLOW_WRITE_A(ra, (gg + 1) & 1, gg + 1 < a.kg ? gg + 1 : gg);  // the other buffer (read last in group g-1)
-        } else {
-          __syncthreads();
-          OFLOW_WRITE_A(ra, 0, gg + 1 < a.kg ? gg + 1 : gg);
-        }
+        __syncthreads();
+        OFLOW_WRITE_A(ra, 0, gg + 1 < a.kg ? gg + 1 : gg);
         const int g2 = gg + 2 < a.kg ? gg + 2 : a.kg - 1;
         OFLOW_LOAD_A(ra, g2);
         __syncthreads();
@@ -807,7 +718,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
           OFLOW_LOAD_A(rar[0], g2);
         }
       }
-      if (!OFLOW_ABL(64)) __syncthreads(); /* B(i+1) [A] visible; every read of step i done before step i+1 overwrites its buffers */
+      __syncthreads(); /* B(i+1) [A] visible; every read of step i done before step i+1 overwrites its buffers */
       // 6-7
       OFLOW_READ_OPS(xah, xal, xbh, xbl, i_ + 1, 0);
       OFLOW_MFMAS(yah, yal, ybh, ybl);
@@ -869,7 +780,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
       }
     }
   if constexpr (EPI == 0 && TY >= kTY) {
-    if (a.stats != nullptr && !OFLOW_ABL(8)) {
+    if (a.stats != nullptr) {
       // instance-norm partials of the conv output (merged by oflow_norm_stats_finalize), from the accumulators: each
       // lane holds one channel of this wave's MT rows (16 pixels per row and lane half); two-pass mean / M2 over its
       // values in fp32, merged with the other lane half (xor 32) and then, per 4-row sub-tile, across the waves that
@@ -1020,7 +931,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
     }
   }
   if constexpr (EPI == 0) {
-    if (a.stats != nullptr && !OFLOW_ABL(8)) {
+    if (a.stats != nullptr) {
       // per-4-row-sub-tile partials from the waves' (count, mean, M2) in sStat, merged in wave order (Chan et al.)
       if constexpr (TY >= kTY) {
         constexpr int NSUB = TY / kTY, WPS = kTY / MT;  // sub-tiles per tile, waves (rows of waves) per sub-tile
@@ -1054,10 +965,9 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
         }
       }
     }
-    if ((a.y0 == nullptr && a.fn == nullptr) || OFLOW_ABL(16)) return;
+    if (a.y0 == nullptr && a.fn == nullptr) return;
   }
 
-  if (OFLOW_ABL(16)) return;
   // S32 / GRU consumers: one thread = one pixel x 8 consecutive channels, KIT items per thread. The GRU state operands
   // of every item (h; z) are loaded first, all in flight at once, then consumed: one memory round trip per epilogue
   // instead of one per item.
@@ -1085,7 +995,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
     }
   }
   // the gates from the hardware exp2 / reciprocal (default; in-process step A/B 19.31 -> 19.05 ms, flows within
-  // 2.8e-5 px, profiles/r04/s15_ab.log); exp flag 256: libm expf / tanhf and IEEE division (A/B only)
+  // 2.8e-5 px, profiles/r04/s15_ab.log); exp flag 256: libm expf / tanhf and IEEE division (the GRU tests run both)
   const bool hwx = (a.exp_flags & 256) == 0;
   constexpr int UNR = EPI == 0 ? 1 : KIT;  // GRU: unrolled (pre[k] in registers); EPI 0: a plain loop
   float gmx = 0.f;  // max |x| of every S32 value this thread stores (one range-guard branch, after the loop)
@@ -1187,7 +1097,7 @@ __global__ __launch_bounds__(64 * WM * WN, WM * WN == 8 ? 1 : 2) void conv_s32_k
 
 inline dim3 conv_grid(const ConvArgs& a, int bn) {
   const int ntiles = a.tiles_x * a.tiles_y * a.B;
-  return OFLOW_XCD_MAP ? dim3(ntiles * (a.npad / bn)) : dim3(ntiles, a.npad / bn);
+  return dim3(ntiles, a.npad / bn);
 }
 
 // LDS-staged kernels: operands prefetched two steps ahead (BD 2). r06 in-process A/B on the replayed 8-pair graph,
@@ -1265,7 +1175,7 @@ int g_small_grid_px = 16384;  // output-pixel count under which the small tiles 
 // profiles/r03/exp/s8b_ab_enc.log). r05, on the replayed graph with the r05 kernels: 457.5 / 457.4 vs 453.6 / 453.9
 // pairs/s (profiles/r05/s58_*.log), so on by default (oflow_exp_set_stats_8row(0) restores the 4-row tiles).
 int g_stats_8row = 1;
-int g_conv_exp_flags = 0;
+int g_conv_exp_flags = 0;  // ConvArgs.exp_flags of every launch (bit 256, the libm gates, is the only one read)
 // BN 64 convs without instance-norm partials (cnet's layer1, convc2, the motion conv) on 8-row tiles (experiments
 // only). r02 adopted them from per-layer timings; in the step (concurrent streams) the 4-row tiles win: interleaved
 // in-process A/B 20.36 vs 20.53-20.55 ms (profiles/r03/exp/s9_ab_bn64.log).
@@ -1515,6 +1425,8 @@ extern "C" int oflow_conv_s32(const oflow_conv_s32_desc* desc, void* stream) {
 // experiment hook (not part of include/oflow.h): the small-grid pixel threshold, for in-process A/B runs (tools/exp)
 extern "C" void oflow_exp_set_small_grid_px(int pixels) { oflow::g_small_grid_px = pixels; }
 extern "C" void oflow_exp_set_stats_8row(int on) { oflow::g_stats_8row = on; }
+// (256, the libm GRU gates, is the only bit left: test_conv_s32_gru_epilogues, test_gru_leaf and the single-valued-gates
+// test run both settings of it)
 extern "C" void oflow_exp_set_conv_flags(int flags) { oflow::g_conv_exp_flags = flags; }
 extern "C" void oflow_exp_set_bn64_8row(int on) { oflow::g_bn64_8row = on; }
 // test hook (not part of include/oflow.h, not thread-safe): which instantiation the last oflow_conv_s32 call launched,

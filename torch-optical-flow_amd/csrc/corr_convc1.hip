@@ -48,7 +48,6 @@ struct C1Args {
   const float* bias;    // [256] or null
   uint8_t* y;           // S32 destination (8 groups of one pixel from y + P * yps)
   long long yps;
-  unsigned long long* stamps;  // diagnostics only (experiment hook): per workgroup 16 clock stamps, or null
 };
 
 // exact n / D for 0 <= n < LIM as (n * M) >> 16 with M = ceil(65536 / D) (checked at compile time)
@@ -80,7 +79,7 @@ constexpr bool magic16_ok(unsigned d, unsigned lim) {
 //     operand registers through a 2-deep ring of k32 groups, each group's load issued right after the MFMAs of the
 //     group two before it. Vector-memory loads retire in issue order, so only a group whose load follows the next
 //     level's gathers waits for them (G = 3: the level's last group).
-// r05 (tools/exp/corr_convc1_variants.hip variant 7, profiles/r05/s13-s14): the r04 kernel's chunk items were decoded
+// r05 (profiles/r05/s13-s14): the r04 kernel's chunk items were decoded
 // per item (query, row, chunk) with per-element masks and selects -- ~680 of 1,190 VALU per wave and level; this
 // mapping and the mix split take the static VALU count from 4,471 to ~2,590, 37.2 -> 35.8 us per 4-pair launch alone.
 // Taps, split values, MFMA order and epilogue are unchanged: bit for bit the r04 kernel's output.
@@ -117,14 +116,6 @@ __global__ __launch_bounds__(kNT, 2) void corr_convc1_kernel(C1Args a) {
   // the gather role: lane = (query of a group of 4 qi, row phase uo, chunk column gk); the wave's 16 queries in 4 groups
   const int gk = lane & 3, uo = (lane >> 2) & 3, qi = lane >> 4;
   constexpr int MR = (PK + 3) / 4;  // rows uo + 4m, m < MR
-  int nst = 0;
-  auto stamp = [&]() {
-    if (a.stamps != nullptr) {
-      if (tid == 0) a.stamps[(size_t)blockIdx.x * 16 + nst] = __builtin_amdgcn_s_memtime();
-      ++nst;
-    }
-  };
-  stamp();
   auto level = [&](int l, int& Hl, int& Wl, int& WB, int& LF, const float*& base) {
     Hl = a.Hl[0]; Wl = a.Wl[0]; WB = a.WB[0]; LF = a.LF[0]; base = a.lv[0];
 #pragma unroll
@@ -205,7 +196,6 @@ __global__ __launch_bounds__(kNT, 2) void corr_convc1_kernel(C1Args a) {
   load_b(0, bq[0]);
   if (nlg > 1) load_b(1, bq[1]);
   gather(0);
-  stamp();
   auto body = [&](int l, auto Pc) {
     constexpr int P = decltype(Pc)::value;
     // ---- 1. chunks -> LDS patches ----
@@ -239,7 +229,6 @@ __global__ __launch_bounds__(kNT, 2) void corr_convc1_kernel(C1Args a) {
       }
     }
     __syncthreads();
-    stamp();
     // ---- 2. next level's gathers, the level after next's windows ----
     if (l + 1 < a.nlev) gather(l + 1);
     if (dwave && l + 2 < a.nlev) decode(l + 2, sC[qd].x, sC[qd].y);
@@ -279,7 +268,6 @@ __global__ __launch_bounds__(kNT, 2) void corr_convc1_kernel(C1Args a) {
       }
     }
     __syncthreads();
-    stamp();
     // ---- 4. the level's MFMAs ----
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -309,7 +297,6 @@ __global__ __launch_bounds__(kNT, 2) void corr_convc1_kernel(C1Args a) {
       const int t2 = l * G + g + 2;
       if (t2 < nlg) load_b(t2, bc);
     }
-    stamp();
   };
   for (int l = 0; l < a.nlev; l += 2) {
     body(l, std::integral_constant<int, 0>{});
@@ -363,11 +350,7 @@ __global__ __launch_bounds__(kNT, 2) void corr_convc1_kernel(C1Args a) {
     *reinterpret_cast<u32x4*>(line) = hw;
     *reinterpret_cast<u32x4*>(line + 64) = lw;
   }
-  if (a.stamps != nullptr) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  stamp();
 }
-
-unsigned long long* g_convc1_stamps = nullptr;  // diagnostics (experiment hook): per-workgroup clock stamps
 
 }  // namespace
 OFLOW_RANGE_FLAG_SETTER(convc1)
@@ -407,15 +390,9 @@ extern "C" int oflow_corr_lookup_convc1_s32(const float* const* d_levels, const 
   a.yps = y_pixel_stride;
   const dim3 grid((a.total + kQM - 1) / kQM);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  a.stamps = g_convc1_stamps;
   if (radius == 4)
     hipLaunchKernelGGL((corr_convc1_kernel<4>), grid, dim3(kNT), 0, s, a);
   else
     hipLaunchKernelGGL((corr_convc1_kernel<3>), grid, dim3(kNT), 0, s, a);
   return launch_status();
-}
-
-// experiment hook (not part of include/oflow.h): a device buffer of 16 clock stamps per workgroup, or null
-extern "C" void oflow_exp_set_convc1_stamps(void* stamps) {
-  oflow::g_convc1_stamps = static_cast<unsigned long long*>(stamps);
 }

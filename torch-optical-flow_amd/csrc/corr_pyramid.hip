@@ -43,7 +43,6 @@ struct PyramidArgs {
   float scale;      // sqrt(C) as torch computes it (float sqrt of float(C))
   float inv_scale;  // exact 1/scale when scale is a power of two (multiply == divide bit-for-bit)
   int scale_pow2;
-  int stagger_cycles, stagger_mode;  // experiments only (oflow_exp_set_pyramid_stagger); 0 in the product
 };
 
 template <bool VEC>
@@ -182,22 +181,8 @@ __device__ __forceinline__ void pyramid_epilogue(const PyramidArgs& p, f32x16 (&
     const int tb = p.WB[0] - (tx0 >> 3);  // tiles of this tile row that exist in the level (>= 1)
     float* const L0b = lvl_base(p, 0, (size_t)b * Nn + i0);
     __syncthreads();  // the main loop's LDS operand reads are done (the scratch aliases them)
-    // experiment (mode bit 4): level-0 stores straight from the accumulators, same addresses, unstaged values
-    const bool direct = (p.stagger_mode & 16) != 0;
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
-      if (direct) {
-        const int tr = lane >> 5, ch = lane & 31;
-        const int y0 = ty0 + 4 * tr;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int i = i0 + wave * 32 + 8 * ps + j;
-          const float4 v = make_float4(acc[j][4 * ps], acc[j][4 * ps + 1], acc[j][4 * ps + 2], acc[j][4 * ps + 3]);
-          if (i < p.N && (y0 >> 2) < p.HB[0] && (ch >> 3) < tb)
-            *reinterpret_cast<float4*>(&L0b[lvl_off32(p, 0, i - i0, y0, tx0) + ch * 4]) = v;
-        }
-        continue;
-      }
 #pragma unroll
       for (int n = 0; n < kTR; ++n)
 #pragma unroll
@@ -233,7 +218,7 @@ __device__ __forceinline__ void pyramid_epilogue(const PyramidArgs& p, f32x16 (&
       }
     }
   }
-  if (p.nlev < 2 || (p.stagger_mode & 8)) return;  // (mode bit 3, experiment: level 0 alone)
+  if (p.nlev < 2) return;
 
   float v2[2][16];
   const int H1 = p.Hl[1], W1 = p.Wl[1];
@@ -287,7 +272,7 @@ __device__ __forceinline__ void pyramid_epilogue(const PyramidArgs& p, f32x16 (&
       const int ql = 4 * j + (lane >> 4);
       const int i = i0 + wave * 32 + ql;
       const float4 v = *reinterpret_cast<const float4*>(&sw[ql * 64 + ch * 4]);
-      if (i < p.N && (y1 >> 2) < p.HB[1] && (ch >> 3) < tb1 && !(p.stagger_mode & 64))
+      if (i < p.N && (y1 >> 2) < p.HB[1] && (ch >> 3) < tb1)
         *reinterpret_cast<float4*>(&lvl_base(p, 1, (size_t)b * Nn + i0)[lvl_off32(p, 1, i - i0, y1, tx0 >> 1) + ch * 4]) = v;
     }
     if (p.nlev < 3) return;
@@ -324,10 +309,10 @@ __device__ __forceinline__ void pyramid_epilogue(const PyramidArgs& p, f32x16 (&
       const int c = lane + 64 * it, ql = c >> 2, part = c & 3;
       const int i = i0 + wave * 32 + ql;
       const float4 v = *reinterpret_cast<const float4*>(&s2[ql * 16 + part * 4]);
-      if (i < p.N && (y2 >> 2) < p.HB[2] && (x2 >> 3) < p.WB[2] && !(p.stagger_mode & 64))
+      if (i < p.N && (y2 >> 2) < p.HB[2] && (x2 >> 3) < p.WB[2])
         *reinterpret_cast<float4*>(&lvl_base(p, 2, (size_t)b * Nn + i0)[lvl_off32(p, 2, i - i0, y2, x2) + part * 4]) = v;
     }
-    if (p.nlev >= 4 && lane < 32 && !(p.stagger_mode & 96)) {
+    if (p.nlev >= 4 && lane < 32) {
       const int y3 = ty0 >> 3, x3 = tx0 >> 3;
       const int i = i0 + wave * 32 + lane;
       const float4 v = *reinterpret_cast<const float4*>(&s2[512 + lane * 4]);
@@ -421,14 +406,6 @@ __global__ __launch_bounds__(kThreads, 2) void corr_pyramid_s32_kernel(PyramidAr
   __shared__ __attribute__((aligned(16))) uint8_t sB[kBN * 128];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (p.stagger_cycles > 0 && blockIdx.z == 0) {  // experiment: start some of the first wave of workgroups late
-    const unsigned id = blockIdx.x;
-    const bool late = (p.stagger_mode & 3) == 1 ? (id >= 256u && id < 512u) : ((id & 1u) && id < 512u);
-    if (late) {
-      const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-      while (__builtin_amdgcn_s_memtime() - t0 < static_cast<unsigned long long>(p.stagger_cycles)) __builtin_amdgcn_s_sleep(8);
-    }
-  }
   int tile, qblk;
   gemm_tile((p.N + kBM - 1) / kBM, p.tiles_x * ((p.H + kTR - 1) / kTR), tile, qblk);
   const int ty0 = (tile / p.tiles_x) * kTR;
@@ -436,7 +413,7 @@ __global__ __launch_bounds__(kThreads, 2) void corr_pyramid_s32_kernel(PyramidAr
   const int i0 = qblk * kBM;
   const int b = blockIdx.z;
   const int ps = (p.C >> 5) * 128;  // bytes per pixel row
-  const int G = (p.stagger_mode & 4) ? 0 : (p.C >> 5);  // experiment (mode bit 2): no main loop, epilogue alone
+  const int G = p.C >> 5;
   const uint8_t* A0 = F1s + (size_t)b * p.N * ps;
   const uint8_t* B0 = F2s + (size_t)b * p.N * ps;
 
@@ -553,15 +530,6 @@ __global__ __launch_bounds__(256) void avgpool2x2_tiled_kernel(const float* __re
 }  // namespace oflow
 
 using namespace oflow;
-
-static int g_pyr_stagger_cycles = 0, g_pyr_stagger_mode = 1;
-// experiment hook (not part of include/oflow.h): delay part of the split pyramid's first workgroups by `cycles`
-// (mode & 3: which ones); ablations: mode & 4 no main loop, & 8 level 0 alone, & 16 level 0 stored unstaged, & 32 no
-// level-3 stores, & 64 no level 1-3 stores (pooled and staged all the same)
-extern "C" void oflow_exp_set_pyramid_stagger(int cycles, int mode) {
-  g_pyr_stagger_cycles = cycles;
-  g_pyr_stagger_mode = mode;
-}
 
 extern "C" long long oflow_corr_tiled_level_floats(int H_l, int W_l) {
   if (H_l <= 0 || W_l <= 0) return 0;
@@ -691,8 +659,6 @@ extern "C" int oflow_corr_pyramid_tiled_s32(const void* d_fmap1_s32, const void*
   int e2 = 0;
   p.scale_pow2 = (frexpf(p.scale, &e2) == 0.5f) ? 1 : 0;
   p.inv_scale = p.scale_pow2 ? 1.0f / p.scale : 0.0f;
-  p.stagger_cycles = g_pyr_stagger_cycles;
-  p.stagger_mode = g_pyr_stagger_mode;
   const dim3 grid(p.tiles_x * ((H + kTR - 1) / kTR) * ((p.N + kBM - 1) / kBM), 1, B);
   hipLaunchKernelGGL((corr_pyramid_s32_kernel<true>), grid, dim3(kThreads), 0, s, p,
                      static_cast<const uint8_t*>(d_fmap1_s32), static_cast<const uint8_t*>(d_fmap2_s32));
