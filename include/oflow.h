@@ -39,6 +39,9 @@
  *                              optical_flow/visualization/methods/meister.py)
  *   oflow_splat_f32, oflow_splat_backward_f32 <- nothing in the reference (csrc/splat.hip, csrc/splat_backward.hip):
  *                              forward warping, the sum / average / linear / softmax splatting of Niklaus and Liu
+ *   oflow_census_loss_f32, oflow_smoothness_loss_f32 and their backwards <- nothing in the reference
+ *                              (csrc/census_loss.hip, csrc/smoothness_loss.hip): the unsupervised training losses of
+ *                              UnFlow / UFlow, scoring a flow against the images alone
  *   oflow_augment_stats_u8, oflow_augment_dense_f32, oflow_augment_sparse_flow_f32 <- methods/raft/data/augmentor.py:43-324
  *                              (FlowAugmentor, SparseFlowAugmentor: PIL ColorJitter, cv2.resize, eraser, flips, crop)
  *                              + methods/raft/data/dataset.py:114-119 (fp32 flow, the dense valid mask)
@@ -770,6 +773,71 @@ int oflow_splat_backward_f32(const float* d_grad_out, const float* d_frame, cons
                              const float* d_out, const float* d_weight, int B, int C, int H, int W, int mode,
                              float* d_grad_frame, float* d_grad_flow, float* d_grad_metric, void* d_workspace,
                              void* stream);
+
+/*
+ * Unsupervised training losses (csrc/census_loss.hip, csrc/smoothness_loss.hip): the ternary census loss over a
+ * patch x patch neighbourhood and the edge-aware smoothness term of UnFlow (Meister et al., AAAI 2018) and UFlow
+ * (Jonschkowski et al., ECCV 2020). The constants (0.81, 0.1, 0.01, 0.4, 0.001; callers default edge_weight to 150) are
+ * the published ones, not tuned here. The reference has no such functions. All tensors contiguous, fp32 4-byte aligned
+ * (else OFLOW_E_ALIGN), fp64 8-byte aligned. No atomics, fixed-order fp64 reductions, grids that depend on the shapes
+ * only: both directions of both losses are bit-identical from run to run.
+ * oflow_census_loss_f32: d_frame0, d_frame1 (B, C, H, W); in a training loss frame1 is the second image already warped
+ *   back. d_mask (B, 1, H, W): fp32 (OFLOW_VALID_F32), bytes with non-zero = 1 (OFLOW_VALID_U8), or ignored, meaning 1
+ *   (OFLOW_VALID_NONE).
+ *     Grey value: g = (sum_c frame_c) * 255 / (image_range * C).
+ *     r = patch / 2; interior pixels are those with r <= y < H - r and r <= x < W - r.
+ *     For an interior pixel p and each of the patch^2 - 1 offsets d != 0:
+ *       delta_k = g_k(p + d) - g_k(p);  t_k = delta_k / sqrt(0.81 + delta_k^2);  e = (t_0 - t_1)^2;
+ *       s(p) = sum_d e / (0.1 + e).
+ *     Robust term: rho(p) = (s(p) + 0.01)^0.4.
+ *     M(p) = mask(p) on interior pixels and 0 elsewhere.
+ *     loss = sum M rho / (sum M + 1e-6), summed over the whole batch; the reductions are fp64 in a fixed order.
+ *   d_loss: 1 float; d_sum_m: 1 double (sum M, which the backward takes); d_s_map: s as (B, 1, H, W) fp32, 0 outside the
+ *   interior, or NULL. If H or W is smaller than patch, or the mask is all zero, the loss is exactly 0. Non-finite frame
+ *   values make the result unspecified. Arithmetic: the channel sums and the differences delta_0, delta_1 and
+ *   delta_0 - delta_1 are formed in fp64 (exact for fp32 frames), scaled and rounded once to fp32; the rest is fp32
+ *   with IEEE sqrt and division, and where delta_0 and delta_1 have the same sign t_0 - t_1 is formed as
+ *   0.81 (delta_0 - delta_1)(delta_0 + delta_1) / ((n_0 n_1)^2 (t_0 + t_1)), n_k = sqrt(0.81 + delta_k^2): the same
+ *   number without the cancellation of two saturated ternaries.
+ *   d_workspace: oflow_census_loss_workspace_bytes(B, H, W) bytes (one row of 2 doubles per 64 x 8 tile), any
+ *   contents. patch outside {3, 5, 7} or a mask kind outside 0..2: OFLOW_E_MODE. B, C, H or W < 1, B > 65535, H * W >
+ *   2^28, image_range not a positive finite number: OFLOW_E_SHAPE (the workspace query returns 0).
+ * oflow_census_loss_backward_f32: the gradients of a scalar with d_grad_loss = dL/dloss (1 float on the device). A
+ *   gather, no atomics of any kind: the gradient of g_k(q) is -sum_d A_k(q, d) + sum_d A_k(q - d, d) with
+ *     A_k(p, d) = c(p) * d[e / (0.1 + e)]/dt_k * dt_k/ddelta_k,
+ *     c(p) = grad_loss * M(p) / (sum M + 1e-6) * 0.4 (s(p) + 0.01)^-0.6,
+ *   and each channel's gradient is the grey gradient times 255 / (image_range * C). d_s_map: the forward's map, or NULL
+ *   to recompute s in the kernel. d_sum_m: the forward's. d_grad_frame0 / d_grad_frame1 (B, C, H, W): a NULL output is
+ *   not formed (both NULL: OFLOW_E_NULL), and the other has the same bits either way. Every element of a requested
+ *   output is written, zeros where nothing contributes (all of it when H or W < patch or the mask is all zero): callers
+ *   need no memset. The mask gets no gradient. An image's gradient bits depend on the rest of the batch only through
+ *   the scalar grad_loss / (sum M + 1e-6). The other argument errors are the forward's.
+ * oflow_smoothness_loss_f32: d_flow (B, 2, H, W) in pixel units, d_image (B, C, H, W).
+ *     Order 1: Dx f = f(x+1) - f(x);  wx = exp(-(edge_weight / image_range) * mean_c |I_c(x+1) - I_c(x)|);
+ *       Lx = mean over (B, 2, H, W-1) of wx * sqrt((Dx f)^2 + 0.001^2); Ly is the mirror image in y;
+ *       loss = (Lx + Ly) / 2.
+ *     Order 2: Dxx f = f(x+2) - 2 f(x+1) + f(x); wx is formed from I(x+2) - I(x); the mean is over (B, 2, H, W-2).
+ *     A direction whose domain is empty contributes 0.
+ *   The flow stencil is formed in fp64 (exact for fp32 flows) and rounded once; the rest is fp32 with expf.
+ *   d_loss: 1 float. d_workspace: oflow_smoothness_loss_workspace_bytes(B, H, W) bytes (one row of 2 doubles per 256
+ *   pixels), any contents. order outside {1, 2}: OFLOW_E_MODE; sizes as the census loss; edge_weight must be finite.
+ * oflow_smoothness_loss_backward_f32: d_grad_flow (B, 2, H, W), every element written; a flow pixel gathers from the 2
+ *   (order 1) or 3 (order 2) differences it takes part in, in each direction. The image is data and gets no gradient.
+ */
+long long oflow_census_loss_workspace_bytes(int B, int H, int W);
+int oflow_census_loss_f32(const float* d_frame0, const float* d_frame1, const void* d_mask, int mask_kind, int B,
+                          int C, int H, int W, int patch, float image_range, float* d_s_map, double* d_workspace,
+                          float* d_loss, double* d_sum_m, void* stream);
+int oflow_census_loss_backward_f32(const float* d_grad_loss, const float* d_frame0, const float* d_frame1,
+                                   const void* d_mask, int mask_kind, const float* d_s_map, const double* d_sum_m,
+                                   int B, int C, int H, int W, int patch, float image_range, float* d_grad_frame0,
+                                   float* d_grad_frame1, void* stream);
+long long oflow_smoothness_loss_workspace_bytes(int B, int H, int W);
+int oflow_smoothness_loss_f32(const float* d_flow, const float* d_image, int B, int C, int H, int W, int order,
+                              float edge_weight, float image_range, double* d_workspace, float* d_loss, void* stream);
+int oflow_smoothness_loss_backward_f32(const float* d_grad_loss, const float* d_flow, const float* d_image, int B,
+                                       int C, int H, int W, int order, float edge_weight, float image_range,
+                                       float* d_grad_flow, void* stream);
 
 /*
  * Training-batch augmentation (csrc/augment.hip): the reference's FlowAugmentor / SparseFlowAugmentor

@@ -131,6 +131,28 @@ __device__ __forceinline__ void window_origin(float cx, float cy, float inv, int
   }
 }
 
+// fp64 reductions of the loss kernels (census_loss.hip, smoothness_loss.hip; flow_metrics.hip's scheme): the xor
+// butterfly inside a wave, then the waves in index order through LDS -- a fixed order, no atomics.
+__device__ __forceinline__ double wave_sum_f64(double x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+// (sum of a, sum of b) over the workgroup (blockDim.x a multiple of 64, at most 1024), valid in thread 0
+__device__ __forceinline__ void block_sum2_f64(double& a, double& b) {
+  __shared__ double red[16][2];
+  a = wave_sum_f64(a);
+  b = wave_sum_f64(b);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = a, red[threadIdx.x >> 6][1] = b;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = b = 0.0;
+    for (int w = 0; w < static_cast<int>(blockDim.x >> 6); ++w) a += red[w][0], b += red[w][1];
+  }
+}
+
+inline bool aligned_to(const void* p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; }
+
 inline int launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? OFLOW_OK : static_cast<int>(e);

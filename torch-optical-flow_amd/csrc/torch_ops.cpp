@@ -45,6 +45,10 @@
 //   splat(frame, flow, metric?, mode) -> (out, weight)           forward warping: sum / average / linear / softmax splatting
 //   splat_backward(grad_out, frame, flow, metric?, out, weight, mode, mask3) -> (grad_frame, grad_flow, grad_metric)
 //                                                                 its autograd (splat.hip, splat_backward.hip; not in the reference)
+//   census_loss(frame0, frame1, mask?, patch, image_range) -> (loss, sum_m, s_map)   the ternary census loss (census_loss.hip)
+//   census_loss_backward(grad_loss, frame0, frame1, mask?, sum_m, s_map, patch, image_range, mask2) -> (grad_frame0, grad_frame1)
+//   smoothness_loss(flow, image, order, edge_weight, image_range) -> loss             edge-aware smoothness (smoothness_loss.hip)
+//   smoothness_loss_backward(grad_loss, flow, image, order, edge_weight, image_range) -> grad_flow
 #include <array>
 #include <torch/library.h>
 #include <ATen/ATen.h>
@@ -1158,6 +1162,147 @@ Tensor3 splat_backward(bool run, const Tensor& gout, const Tensor& frame, const 
   return Tensor3(gfr, gfl, gme);
 }
 
+// ---------------------------------------------------------------- unsupervised losses (census_loss.hip, smoothness_loss.hip)
+// the mask as the C ABI takes it: bool -> bytes, any float dtype -> fp32, none -> OFLOW_VALID_NONE
+int loss_mask(const c10::optional<Tensor>& mask, Tensor& keep, const void*& ptr) {
+  ptr = nullptr;
+  if (!mask.has_value()) return OFLOW_VALID_NONE;
+  if (mask->scalar_type() == at::kBool) {
+    keep = mask->contiguous();
+    ptr = keep.data_ptr<bool>();
+    return OFLOW_VALID_U8;
+  }
+  keep = mask->to(at::kFloat).contiguous();
+  ptr = keep.data_ptr<float>();
+  return OFLOW_VALID_F32;
+}
+
+void check_census(const Tensor& f0, const Tensor& f1, const c10::optional<Tensor>& mask, int64_t patch, double range,
+                  bool run, const char* what) {
+  if (run) {
+    check_on_gpu(f0, "frame0", what), check_on_gpu(f1, "frame1", what);
+    if (mask.has_value()) check_on_gpu(*mask, "mask", what);
+  }
+  TORCH_CHECK(f0.dim() == 4 && f0.sizes() == f1.sizes(), what, ": frame0 ", f0.sizes(), " and frame1 ", f1.sizes(),
+              " must be equal (B, C, H, W)");
+  TORCH_CHECK(f0.device() == f1.device(), what, ": frame0 and frame1 are on different devices");
+  const int64_t b = f0.size(0), h = f0.size(2), w = f0.size(3);
+  if (mask.has_value()) {
+    TORCH_CHECK(mask->dim() == 4 && mask->size(0) == b && mask->size(1) == 1 && mask->size(2) == h && mask->size(3) == w,
+                what, ": mask must be (B, 1, H, W) = (", b, ", 1, ", h, ", ", w, "), got ", mask->sizes());
+    TORCH_CHECK(mask->scalar_type() == at::kBool || mask->is_floating_point(), what, ": mask must be float or bool, got ",
+                mask->scalar_type());
+    TORCH_CHECK(mask->device() == f0.device(), what, ": frame0 and mask are on different devices");
+  }
+  TORCH_CHECK(patch == 3 || patch == 5 || patch == 7, what, ": patch ", patch, " is not one of 3, 5, 7");
+  TORCH_CHECK(range > 0 && std::isfinite(range), what, ": image_range ", range, " must be positive and finite");
+  TORCH_CHECK(b <= 65535 && f0.size(1) <= INT_MAX && h * w <= (int64_t(1) << 28), what, ": frames ", f0.sizes(),
+              " are past the kernels' range (B <= 65535, H*W <= 2^28)");
+}
+
+// (loss fp32 0-dim, sum M fp64 0-dim, s (B, 1, H, W) fp32); any float dtype or strides, as warp
+Tensor3 census_loss(bool run, const Tensor& frame0, const Tensor& frame1, const c10::optional<Tensor>& mask, int64_t patch,
+                    double range) {
+  const char* what = "census_loss";
+  check_census(frame0, frame1, mask, patch, range, run, what);
+  const int64_t b = frame0.size(0), c = frame0.size(1), h = frame0.size(2), w = frame0.size(3);
+  const auto opt = frame0.options().dtype(at::kFloat);
+  Tensor loss = at::empty({}, opt), sum_m = at::empty({}, opt.dtype(at::kDouble)), s_map = at::empty({b, 1, h, w}, opt);
+  if (!run) return Tensor3(loss, sum_m, s_map);
+  if (frame0.numel() == 0) return Tensor3(loss.zero_(), sum_m.zero_(), s_map.zero_());
+  Tensor f0 = gpu_f32(frame0, "frame0", what), f1 = gpu_f32(frame1, "frame1", what), mk;
+  const void* mp;
+  const int kind = loss_mask(mask, mk, mp);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(f0.device());
+  Tensor ws = at::empty({oflow_census_loss_workspace_bytes((int)b, (int)h, (int)w) / 8}, opt.dtype(at::kDouble));
+  check_status(oflow_census_loss_f32(f0.data_ptr<float>(), f1.data_ptr<float>(), mp, kind, (int)b, (int)c, (int)h, (int)w,
+                                     (int)patch, (float)range, s_map.data_ptr<float>(), ws.data_ptr<double>(),
+                                     loss.data_ptr<float>(), sum_m.data_ptr<double>(), cur_stream()),
+               what);
+  return Tensor3(loss, sum_m, s_map);
+}
+
+std::tuple<Tensor, Tensor> census_loss_backward(bool run, const Tensor& gloss, const Tensor& frame0, const Tensor& frame1,
+                                                const c10::optional<Tensor>& mask, const Tensor& sum_m,
+                                                const Tensor& s_map, int64_t patch, double range, std::array<bool, 2> om) {
+  const char* what = "census_loss backward";
+  if (run) check_on_gpu(gloss, "grad_loss", what), check_on_gpu(sum_m, "sum_m", what), check_on_gpu(s_map, "s_map", what);
+  check_census(frame0, frame1, mask, patch, range, run, what);
+  const int64_t b = frame0.size(0), c = frame0.size(1), h = frame0.size(2), w = frame0.size(3);
+  TORCH_CHECK(gloss.numel() == 1 && sum_m.numel() == 1, what, ": grad_loss and sum_m must hold one element each");
+  TORCH_CHECK(s_map.dim() == 4 && s_map.size(0) == b && s_map.size(1) == 1 && s_map.size(2) == h && s_map.size(3) == w,
+              what, ": s_map must have the shape (B, 1, H, W) = (", b, ", 1, ", h, ", ", w, "), got ", s_map.sizes());
+  TORCH_CHECK(gloss.device() == frame0.device() && sum_m.device() == frame0.device() && s_map.device() == frame0.device(),
+              what, ": all tensors must be on one device");
+  const auto opt = frame0.options().dtype(at::kFloat);
+  Tensor g0 = wanted(om[0], {b, c, h, w}, opt), g1 = wanted(om[1], {b, c, h, w}, opt);
+  if (!run || !(om[0] || om[1]) || frame0.numel() == 0) return {g0, g1};
+  Tensor go = gpu_f32(gloss, "grad_loss", what), f0 = gpu_f32(frame0, "frame0", what), f1 = gpu_f32(frame1, "frame1", what);
+  Tensor sm = sum_m.to(at::kDouble).contiguous(), sp = gpu_f32(s_map, "s_map", what), mk;
+  const void* mp;
+  const int kind = loss_mask(mask, mk, mp);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(f0.device());
+  check_status(oflow_census_loss_backward_f32(go.data_ptr<float>(), f0.data_ptr<float>(), f1.data_ptr<float>(), mp, kind,
+                                              sp.data_ptr<float>(), sm.data_ptr<double>(), (int)b, (int)c, (int)h, (int)w,
+                                              (int)patch, (float)range, om[0] ? g0.data_ptr<float>() : nullptr,
+                                              om[1] ? g1.data_ptr<float>() : nullptr, cur_stream()),
+               what);
+  return {g0, g1};
+}
+
+void check_smoothness(const Tensor& flow, const Tensor& image, int64_t order, double edge_weight, double range, bool run,
+                      const char* what) {
+  if (run) check_on_gpu(flow, "flow", what), check_on_gpu(image, "image", what);
+  TORCH_CHECK(image.dim() == 4, what, ": image must be (B, C, H, W), got ", image.sizes());
+  const int64_t b = image.size(0), h = image.size(2), w = image.size(3);
+  TORCH_CHECK(flow.dim() == 4 && flow.size(0) == b && flow.size(1) == 2 && flow.size(2) == h && flow.size(3) == w, what,
+              ": flow must be (B, 2, H, W) = (", b, ", 2, ", h, ", ", w, "), got ", flow.sizes());
+  TORCH_CHECK(flow.device() == image.device(), what, ": flow and image are on different devices");
+  TORCH_CHECK(order == 1 || order == 2, what, ": order ", order, " is not 1 or 2");
+  TORCH_CHECK(range > 0 && std::isfinite(range) && std::isfinite(edge_weight), what, ": image_range ", range,
+              " must be positive and finite and edge_weight ", edge_weight, " finite");
+  TORCH_CHECK(b <= 65535 && image.size(1) <= INT_MAX && h * w <= (int64_t(1) << 28), what, ": image ", image.sizes(),
+              " is past the kernels' range (B <= 65535, H*W <= 2^28)");
+}
+
+Tensor smoothness_loss(bool run, const Tensor& flow, const Tensor& image, int64_t order, double edge_weight, double range) {
+  const char* what = "smoothness_loss";
+  check_smoothness(flow, image, order, edge_weight, range, run, what);
+  const int64_t b = image.size(0), c = image.size(1), h = image.size(2), w = image.size(3);
+  const auto opt = flow.options().dtype(at::kFloat);
+  Tensor loss = at::empty({}, opt);
+  if (!run) return loss;
+  if (image.numel() == 0) return loss.zero_();
+  Tensor fl = gpu_f32(flow, "flow", what), im = gpu_f32(image, "image", what);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(fl.device());
+  Tensor ws = at::empty({oflow_smoothness_loss_workspace_bytes((int)b, (int)h, (int)w) / 8}, opt.dtype(at::kDouble));
+  check_status(oflow_smoothness_loss_f32(fl.data_ptr<float>(), im.data_ptr<float>(), (int)b, (int)c, (int)h, (int)w,
+                                         (int)order, (float)edge_weight, (float)range, ws.data_ptr<double>(),
+                                         loss.data_ptr<float>(), cur_stream()),
+               what);
+  return loss;
+}
+
+Tensor smoothness_loss_backward(bool run, const Tensor& gloss, const Tensor& flow, const Tensor& image, int64_t order,
+                                double edge_weight, double range) {
+  const char* what = "smoothness_loss backward";
+  if (run) check_on_gpu(gloss, "grad_loss", what);
+  check_smoothness(flow, image, order, edge_weight, range, run, what);
+  TORCH_CHECK(gloss.numel() == 1, what, ": grad_loss must hold one element");
+  TORCH_CHECK(gloss.device() == flow.device(), what, ": all tensors must be on one device");
+  const int64_t b = image.size(0), c = image.size(1), h = image.size(2), w = image.size(3);
+  Tensor gf = at::empty({b, 2, h, w}, flow.options().dtype(at::kFloat));
+  if (!run || gf.numel() == 0) return gf;
+  if (c == 0) return gf.zero_();
+  Tensor go = gpu_f32(gloss, "grad_loss", what), fl = gpu_f32(flow, "flow", what), im = gpu_f32(image, "image", what);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(fl.device());
+  check_status(oflow_smoothness_loss_backward_f32(go.data_ptr<float>(), fl.data_ptr<float>(), im.data_ptr<float>(), (int)b,
+                                                  (int)c, (int)h, (int)w, (int)order, (float)edge_weight, (float)range,
+                                                  gf.data_ptr<float>(), cur_stream()),
+               what);
+  return gf;
+}
+
 // ---------------------------------------------------------------- training-batch augmentation (augment.hip)
 Tensor4 augment_batch(bool run, const Tensor& img1, const Tensor& img2, const Tensor& flow,
                       const c10::optional<Tensor>& valid, const Tensor& params, int64_t ch, int64_t cw) {
@@ -1277,6 +1422,10 @@ TORCH_LIBRARY(oflow, m) {
   m.def("fb_consistency(Tensor flow_fw, Tensor flow_bw, float alpha, float beta, bool both, bool with_error) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("splat(Tensor frame, Tensor flow, Tensor? metric, int mode) -> (Tensor out, Tensor weight)");
   m.def("splat_backward(Tensor grad_out, Tensor frame, Tensor flow, Tensor? metric, Tensor out, Tensor weight, int mode, bool[3] output_mask) -> (Tensor, Tensor, Tensor)");
+  m.def("census_loss(Tensor frame0, Tensor frame1, Tensor? mask, int patch, float image_range) -> (Tensor loss, Tensor sum_m, Tensor s_map)");
+  m.def("census_loss_backward(Tensor grad_loss, Tensor frame0, Tensor frame1, Tensor? mask, Tensor sum_m, Tensor s_map, int patch, float image_range, bool[2] output_mask) -> (Tensor, Tensor)");
+  m.def("smoothness_loss(Tensor flow, Tensor image, int order, float edge_weight, float image_range) -> Tensor");
+  m.def("smoothness_loss_backward(Tensor grad_loss, Tensor flow, Tensor image, int order, float edge_weight, float image_range) -> Tensor");
 
   bind<&corr_pyramid>(m, "corr_pyramid");
   bind<&corr_pyramid_tiled>(m, "corr_pyramid_tiled");
@@ -1313,4 +1462,8 @@ TORCH_LIBRARY(oflow, m) {
   bind<&fb_consistency>(m, "fb_consistency");
   bind<&splat>(m, "splat");
   bind<&splat_backward>(m, "splat_backward");
+  bind<&census_loss>(m, "census_loss");
+  bind<&census_loss_backward>(m, "census_loss_backward");
+  bind<&smoothness_loss>(m, "smoothness_loss");
+  bind<&smoothness_loss_backward>(m, "smoothness_loss_backward");
 }

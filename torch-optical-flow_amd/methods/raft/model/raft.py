@@ -216,6 +216,25 @@ class RAFT(nn.Module):
         self.last_train_metrics = metrics
         return loss
 
+    def unsupervised_step(self, batch: Tuple[Tensor, Tensor], batch_idx: int = 0, w_census: float = 1.0,
+                          w_smooth: float = 1.0, smooth_order: int = 1) -> Tensor:
+        """One training batch ``(img0, img1)`` without ground truth (an addition; the reference has none): both flow
+        directions from ``forward_bidirectional`` with ``hparams.iters`` refinements, the occlusion masks of the last
+        predictions under ``no_grad`` (``optical_flow.fb_consistency(..., both=True)``), and
+        ``unsupervised_sequence_loss`` with ``hparams.gamma`` summed over both directions with ``mask = ~occluded``.
+        Returns the loss for the caller's ``backward()``; like ``training_step`` it does no logging and has no
+        optimizer, and nothing in it synchronises with the host. The weights are plain keyword defaults and untuned:
+        the papers this follows (UnFlow, UFlow) weigh the smoothness term per dataset."""
+        from optical_flow import fb_consistency
+
+        img0, img1 = batch
+        preds_fw, preds_bw = self.forward_bidirectional(img0, img1, iters=self.hparams.iters)
+        with torch.no_grad():
+            occ_fw, occ_bw = fb_consistency(preds_fw[-1], preds_bw[-1], both=True)
+        kw = dict(gamma=self.hparams.gamma, w_census=w_census, w_smooth=w_smooth, smooth_order=smooth_order)
+        return (unsupervised_sequence_loss(preds_fw, img0, img1, mask=~occ_fw, **kw)
+                + unsupervised_sequence_loss(preds_bw, img1, img0, mask=~occ_bw, **kw))
+
     # -- evaluation --------------------------------------------------------------------------------------
     def validation_step(self, batch: Tuple[Tensor, Tensor, Tensor, Tensor], batch_idx: int = 0, stage: str = "sintel") -> None:
         """One evaluation batch ``(img0, img1, flow_gt, valid)`` (`raft.py:183-196`): pad for ``stage`` (the reference
@@ -635,3 +654,39 @@ def sequence_loss_torch(flow_preds, flow_gt: Tensor, valid: Tensor, weights, max
     epe = torch.sum((flow_preds[-1].detach() - flow_gt) ** 2, dim=1).sqrt()[mask]
     px = torch.stack([(epe < t).float().mean() for t in (1, 3, 5)]).tolist()
     return loss, {"1px": px[0], "3px": px[1], "5px": px[2]}
+
+
+def unsupervised_sequence_loss(
+    flow_preds: List[Tensor],
+    image0: Tensor,
+    image1: Tensor,
+    mask: Optional[Tensor] = None,
+    gamma: float = 0.8,
+    w_census: float = 1.0,
+    w_smooth: float = 1.0,
+    smooth_order: int = 1,
+) -> Tensor:
+    """``sequence_loss`` without ground truth (an addition; the reference has none): every prediction is scored against
+    the images alone,
+
+        ``sum_i gamma^(n-1-i) [w_census * census_loss(image0, warp(image1, normalize(flow_i), align_corners=True), mask)
+        + w_smooth * smoothness_loss(flow_i, image0, order=smooth_order)]``
+
+    with ``optical_flow.census_loss`` / ``smoothness_loss`` (native kernels on the GPU, forward and backward) and the
+    differentiable ``optical_flow.warp``. ``mask`` (B, 1, H, W), float or bool, is the census term's: in the intended
+    use ``~occluded`` from ``optical_flow.fb_consistency``. ``align_corners=True`` is deliberate: it is the convention
+    ``normalize`` uses, and with ``False`` ``warp`` is not the identity at zero flow (quirk Q8 in
+    optical_flow/operator/operator.py). The weights are plain defaults, untuned. Images in [0, 255]."""
+    from optical_flow import census_loss, normalize, smoothness_loss, warp, warp_grid
+
+    n = len(flow_preds)
+    loss = 0.0
+    for i, flow in enumerate(flow_preds):
+        if flow.is_cuda:
+            warped = warp(image1, normalize(flow), align_corners=True)
+        else:  # (``warp`` has no CPU path: the same sampling through ATen, as the reference's ``warp`` is written)
+            grid = warp_grid(normalize(flow).permute(0, 2, 3, 1))
+            warped = F.grid_sample(image1, grid.to(image1.dtype), mode="bilinear", padding_mode="border", align_corners=True)
+        term = w_census * census_loss(image0, warped, mask) + w_smooth * smoothness_loss(flow, image0, order=smooth_order)
+        loss = loss + gamma ** (n - 1 - i) * term
+    return loss

@@ -6,12 +6,14 @@ gfx950 HIP kernel through the C ABI of ``liboflow_hip.so`` (include/oflow.h). Th
 (Middlebury, PFM, KITTI) with the file payload laid out on the device. ``fb_consistency`` (an addition) gives the
 forward-backward occlusion masks of a flow pair in one kernel launch; ``splat`` (an addition) warps a frame forwards
 along a flow (sum / average / linear / softmax splatting, bit-reproducible, differentiable) and ``interpolate_frame``
-blends two such warps into an in-between frame.
+blends two such warps into an in-between frame. ``census_loss`` and ``smoothness_loss`` (``optical_flow.losses``, an
+addition) score a flow against the images alone: the unsupervised training losses of UnFlow / UFlow on fused kernels.
 """
 from .io.read_write import read, write
+from .losses import census_loss, smoothness_loss
 from .operator.operator import (denormalize, fb_consistency, integrate, interpolate_frame, normalize, resize, scale, splat,
                                 warp, warp_grid)
 from .visualization.flow2rgb import colorwheel, flow2rgb
 
-__all__ = ["colorwheel", "denormalize", "fb_consistency", "flow2rgb", "integrate", "interpolate_frame", "normalize", "read",
-           "resize", "scale", "splat", "warp", "warp_grid", "write"]
+__all__ = ["census_loss", "colorwheel", "denormalize", "fb_consistency", "flow2rgb", "integrate", "interpolate_frame", "normalize", "read",
+           "resize", "scale", "smoothness_loss", "splat", "warp", "warp_grid", "write"]

@@ -131,6 +131,12 @@ def _signatures():
         "oflow_splat_workspace_bytes": (L, [I, I, I, I]),
         "oflow_splat_f32": (I, [P, P, P, I, I, I, I, I, P, P, P, P]),
         "oflow_splat_backward_f32": (I, [P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P]),
+        "oflow_census_loss_workspace_bytes": (L, [I, I, I]),
+        "oflow_census_loss_f32": (I, [P, P, P, I, I, I, I, I, I, F, P, P, P, P, P]),
+        "oflow_census_loss_backward_f32": (I, [P, P, P, P, I, P, P, I, I, I, I, I, F, P, P, P]),
+        "oflow_smoothness_loss_workspace_bytes": (L, [I, I, I]),
+        "oflow_smoothness_loss_f32": (I, [P, P, I, I, I, I, I, F, F, P, P, P]),
+        "oflow_smoothness_loss_backward_f32": (I, [P, P, P, I, I, I, I, I, F, F, P, P]),
     }
 
 
@@ -494,6 +500,26 @@ def splat(frame: torch.Tensor, flow: torch.Tensor, metric: Optional[torch.Tensor
 
 
 AUG_PARAM_DOUBLES = 36  # include/oflow.h OFLOW_AUG_PARAM_DOUBLES
+
+
+def census_loss(frame0: torch.Tensor, frame1: torch.Tensor, mask: Optional[torch.Tensor], patch: int, image_range: float):
+    """The ternary census loss of two (B, C, H, W) frames (``torch.ops.oflow.census_loss``, include/oflow.h
+    oflow_census_loss_f32): (loss fp32 0-dim, sum M fp64 0-dim, s (B, 1, H, W) fp32), bit-reproducible. Differentiable in
+    the two frames (native gather, csrc/census_loss.hip); sum M and the map are not."""
+    what = "census_loss"
+    f0, f1 = _tensor(frame0, "frame0", what), _tensor(frame1, "frame1", what)
+    me = None if mask is None else _tensor(mask, "mask", what)
+    return _run(what, f0.device, ops().census_loss, f0, f1, me, int(patch), float(image_range))
+
+
+def smoothness_loss(flow: torch.Tensor, image: torch.Tensor, order: int, edge_weight: float, image_range: float):
+    """The edge-aware smoothness of a (B, 2, H, W) flow in pixel units under a (B, C, H, W) image
+    (``torch.ops.oflow.smoothness_loss``, include/oflow.h oflow_smoothness_loss_f32): the fp32 0-dim loss,
+    bit-reproducible, differentiable in the flow (native gather, csrc/smoothness_loss.hip)."""
+    what = "smoothness_loss"
+    fl, im = _tensor(flow, "flow", what), _tensor(image, "image", what)
+    return _run(what, fl.device, ops().smoothness_loss, fl, im.detach(), int(order), float(edge_weight),
+                float(image_range))
 
 
 def augment_batch(img1: torch.Tensor, img2: torch.Tensor, flow: torch.Tensor, valid: Optional[torch.Tensor],

@@ -62,6 +62,14 @@ in the flows and has no gradient, and the residual is returned for inspection an
     each source's four taps: no float atomics in either direction, bit-reproducible. Only the gradients
     ``needs_input_grad`` asks for are formed; the softmax mode's shift by the image's metric maximum counts as a
     constant. ``splat`` and ``splat_backward`` are listed in ``OPS_SPLAT``, not in ``OPS``.
+  * ``census_loss`` / ``smoothness_loss`` (``optical_flow.losses``, the unsupervised training losses): the census
+    forward (csrc/census_loss.hip) returns (loss, sum M, s map); the frames, the mask and the last two are saved, sum M
+    and the map are not differentiable, and the backward (``census_loss_backward``) is a tiled gather that takes s from
+    the saved map instead of recomputing it. Only the frame gradients ``needs_input_grad`` asks for are formed; the mask
+    gets none. ``smoothness_loss`` saves the flow and the image; its backward (``smoothness_loss_backward``,
+    csrc/smoothness_loss.hip) gathers each flow pixel's two or three differences per direction, and the image, which
+    is data, gets none. No atomics and fixed-order fp64 sums in both directions: bit-reproducible. The four ops are
+    listed in ``OPS_LOSSES``, not in ``OPS`` or ``OPS_SPLAT``.
 """
 from __future__ import annotations
 
@@ -112,6 +120,14 @@ OPS = (
 OPS_SPLAT = (
     "splat",
     "splat_backward",
+)
+# the unsupervised training losses, kept apart likewise; their schemas are recorded in
+# tests/golden/op_schemas_losses.txt
+OPS_LOSSES = (
+    "census_loss",
+    "census_loss_backward",
+    "smoothness_loss",
+    "smoothness_loss_backward",
 )
 _loaded = False
 
@@ -299,6 +315,36 @@ def _splat_backward(ctx, grad_out, _grad_weight):
         (g_metric.to(metric.dtype) if need[2] else None), None
 
 
+def _census_setup(ctx, inputs, output):
+    frame0, frame1, mask, patch, image_range = inputs
+    _loss, sum_m, s_map = output
+    ctx.save_for_backward(frame0, frame1, mask, sum_m, s_map)  # s is taken from the map, not recomputed
+    ctx.args = (patch, image_range)
+    ctx.mark_non_differentiable(sum_m, s_map)
+
+
+def _census_backward(ctx, grad_loss, _grad_sum_m, _grad_s_map):
+    frame0, frame1, mask, sum_m, s_map = ctx.saved_tensors
+    need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])]
+    g0, g1 = torch.ops.oflow.census_loss_backward(grad_loss.contiguous(), frame0, frame1, mask, sum_m, s_map, *ctx.args,
+                                                  need)
+    return (g0.to(frame0.dtype) if need[0] else None), (g1.to(frame1.dtype) if need[1] else None), None, None, None
+
+
+def _smoothness_setup(ctx, inputs, output):
+    flow, image, order, edge_weight, image_range = inputs
+    ctx.save_for_backward(flow, image)
+    ctx.args = (order, edge_weight, image_range)
+
+
+def _smoothness_backward(ctx, grad_loss):
+    flow, image = ctx.saved_tensors
+    if not ctx.needs_input_grad[0]:
+        return None, None, None, None, None
+    g = torch.ops.oflow.smoothness_loss_backward(grad_loss.contiguous(), flow, image, *ctx.args)
+    return g.to(flow.dtype), None, None, None, None
+
+
 def _register_autograd() -> None:
     ops = torch.ops.oflow
 
@@ -319,3 +365,5 @@ def _register_autograd() -> None:
     reg("oflow::batch_norm_act",
         *_param_layer_formula(ops.batch_norm_act_backward, n_saved=3, n_plain=2, saves_statistics=True))
     reg("oflow::splat", _splat_setup, _splat_backward)
+    reg("oflow::census_loss", _census_setup, _census_backward)
+    reg("oflow::smoothness_loss", _smoothness_setup, _smoothness_backward)
