@@ -42,6 +42,8 @@
  *   oflow_census_loss_f32, oflow_smoothness_loss_f32 and their backwards <- nothing in the reference
  *                              (csrc/census_loss.hip, csrc/smoothness_loss.hip): the unsupervised training losses of
  *                              UnFlow / UFlow, scoring a flow against the images alone
+ *   oflow_ssim_loss_f32, oflow_charbonnier_loss_f32 and their backwards <- nothing in the reference
+ *                              (csrc/photometric_loss.hip): the SSIM and robust L1 photometric terms of the same methods
  *   oflow_augment_stats_u8, oflow_augment_dense_f32, oflow_augment_sparse_flow_f32 <- methods/raft/data/augmentor.py:43-324
  *                              (FlowAugmentor, SparseFlowAugmentor: PIL ColorJitter, cv2.resize, eraser, flips, crop)
  *                              + methods/raft/data/dataset.py:114-119 (fp32 flow, the dense valid mask)
@@ -838,6 +840,92 @@ int oflow_smoothness_loss_f32(const float* d_flow, const float* d_image, int B, 
 int oflow_smoothness_loss_backward_f32(const float* d_grad_loss, const float* d_flow, const float* d_image, int B,
                                        int C, int H, int W, int order, float edge_weight, float image_range,
                                        float* d_grad_flow, void* stream);
+
+/*
+ * Photometric losses (csrc/photometric_loss.hip): SSIM and Charbonnier (robust L1), the terms the unsupervised methods
+ * use beside or instead of the census loss (UnFlow and UFlow ablate between the three; ARFlow's default is
+ * L1 + SSIM + ternary). The reference has no such functions. Frames d_frame0, d_frame1 (B, C, H, W); in a training loss
+ * frame1 is the second image already warped back. d_mask (B, 1, H, W) and mask_kind as for the census loss. All tensors
+ * contiguous, fp32 4-byte aligned (else OFLOW_E_ALIGN), fp64 8-byte aligned. No atomics, fixed-order fp64 reductions,
+ * grids that depend on the shapes only: both directions of both losses are bit-identical from run to run.
+ * oflow_ssim_loss_f32: window in {3, 5, 7, 9, 11}, r = window / 2. weights: window floats in HOST memory, the 1-D
+ *   weights w[i] of the separable window w(dy, dx) = w[dy] w[dx] (the product of the two fp32 values as a real number).
+ *   Callers normalise a box (1 / window) or a Gaussian (exp(-(i - r)^2 / (2 sigma^2))) in float64 and round to fp32;
+ *   the fp32 values are the contract's weights, so S = (sum_i w[i])^2 is 1 only to rounding, and k = 1 - S.
+ *   c1 = (k1 image_range)^2 and c2 = (k2 image_range)^2, likewise formed in float64 and rounded to fp32 by the caller;
+ *   the frames are used as they are (no division of the input).
+ *     Interior pixels: r <= y < H - r and r <= x < W - r (a "valid" filter, as the census loss).
+ *     For an interior pixel p and channel c, sums over the window offsets d:
+ *       mu_x = sum w(d) x(p + d),  mu_y likewise;
+ *       v_x = sum w(d) (x(p + d) - mu_x)^2,  v_y likewise;  c_xy = sum w(d) (x(p + d) - mu_x)(y(p + d) - mu_y);
+ *       SSIM_c = (2 mu_x mu_y + c1)(2 c_xy + c2) / ((mu_x^2 + mu_y^2 + c1)(v_x + v_y + c2)).
+ *     d(p) = mean_c (1 - SSIM_c) / 2, not clamped (with c1, c2 > 0 it lies in [0, 1] already).
+ *     M(p) = mask(p) on interior pixels and 0 elsewhere.
+ *     loss = sum M d / (sum M + 1e-6), summed over the whole batch; the reductions are fp64 in a fixed order.
+ *   Arithmetic: 1 - SSIM from the quotient above loses everything on near-identical frames, so it is formed as
+ *       A1 = 2 mu_x mu_y + c1,  B2 = v_x + v_y + c2,  dm = mu_x - mu_y = sum w(d) e(p + d),  e = x - y,
+ *       v_d = sum w(d) (e(p + d) - dm)^2  (= v_x + v_y - 2 c_xy),
+ *       1 - SSIM_c = (A1 v_d + dm^2 B2) / ((A1 + dm^2) B2),
+ *   every term non-negative on non-negative frames; e is formed in fp64 (exact for fp32 frames) and rounded once, the
+ *   rest is fp32 with IEEE division. The window sums run row by row (columns first) with fused multiply-adds over the
+ *   values less the centre pixel's, so that a flat neighbourhood keeps its small deviations: for t in (x, y, e)
+ *       o_t = sum w(d) (t(p + d) - t(p)) - k t(p)  (= mu_t - t(p)),  mu_t = t(p) + o_t,
+ *       v_t = sum w(d) ((t(p + d) - t(p)) - o_t)^2.
+ *   d_loss: 1 float; d_sum_m: 1 double (sum M, which the backward takes); d_ssim_map: mean_c SSIM_c = 1 - (sum_c (1 -
+ *   SSIM_c)) / C as (B, 1, H, W) fp32, 0 outside the interior, or NULL. If H or W is smaller than window, or the mask is
+ *   all zero, the loss is exactly 0; on identical non-negative frames it is exactly 0 too. Non-finite frame values
+ *   make the result unspecified. d_workspace: oflow_ssim_loss_workspace_bytes(B, H, W) bytes (one row of 2 doubles per
+ *   64 x 8 tile), any contents. A window outside the set or a mask kind outside 0..2: OFLOW_E_MODE. B, C, H or W < 1,
+ *   B > 65535, H * W > 2^28, c1 or c2 not a positive finite number, a non-finite weight: OFLOW_E_SHAPE (the workspace
+ *   query returns 0). NULL frames, weights, workspace or outputs (the map excepted): OFLOW_E_NULL. Nothing is launched
+ *   on an error.
+ * oflow_ssim_loss_backward_f32: the gradients of a scalar with d_grad_loss = dL/dloss (1 float on the device), from the
+ *   cancellation-free form as well. With F = 1 - SSIM_c of pixel p, l = A1 / T, T = A1 + dm^2, csl = v_d / B2,
+ *   cs = 1 - csl:
+ *       dF/dmu_x = Fx = 2 cs dm (mu_y (mu_x + mu_y) + c1) / T^2,   dF/dmu_y = Fy = -2 cs dm (mu_x (mu_x + mu_y) + c1) / T^2,
+ *       dF/dv_x = dF/dv_y = l cs / B2,   dF/dc_xy = -2 l / B2 = -G,
+ *       dmu_x/dx(q) = w(d),  dv_x/dx(q) = 2 w(d) (x(q) - mu_x - k mu_x),  dc_xy/dx(q) = w(d) (y(q) - mu_y - k mu_y),
+ *   d = q - p, with G = 2 l / B2, so that
+ *       dF(p)/dx(q) = w(q - p) (Fx' + G (cs (x(q) - mu_x) - (y(q) - mu_y))),   Fx' = Fx - k G (dm - csl mu_x),
+ *       dF(p)/dy(q) = w(q - p) (Fy' + G (cs (y(q) - mu_y) - (x(q) - mu_x))),   Fy' = Fy + k G (dm + csl mu_y).
+ *   cs (x - mu_x) - (y - mu_y) = (e(q) - dm) - csl (x(q) - mu_x): the kernel takes the left side, with
+ *   cs = (2 c_xy + c2) / B2, where v_d > B2 / 2 (dissimilar frames, cs near 0) and the right side, with cs = 1 - csl,
+ *   elsewhere (similar frames, where x - mu_x and y - mu_y nearly cancel); and it takes every t(q) - mu_t as
+ *   (t(q) - t(p)) - o_t, the o_t above. In either case
+ *       dF(p)/dx(q) = w(q - p) (Px(p) + al(p) (x(q) - x(p)) + be(p) (y(q) - y(p)) + ga(p) (e(q) - e(p))),
+ *       dF(p)/dy(q) = w(q - p) (Py(p) + al(p) (y(q) - y(p)) + be(p) (x(q) - x(p)) - ga(p) (e(q) - e(p))),
+ *   (al, be, ga) = (G cs, -G, 0) or (-G csl, 0, G), Px = Fx' - (al o_x + be o_y + ga o_e), Py = Fy' - (al o_y + be o_x -
+ *   ga o_e), and the gradient of x_c(q) is the window-weighted gather of these per-pixel coefficient planes over the
+ *   pixels p whose window holds q, each scaled by g(p) = grad_loss * M(p) / (sum M + 1e-6) / (2 C). The statistics
+ *   are recomputed from the frames. d_grad_frame0 / d_grad_frame1 (B, C, H, W): a NULL output is not formed (both
+ *   NULL: OFLOW_E_NULL), and the other has the same bits either way. Every element of a requested output is written,
+ *   zeros where nothing contributes (all of it when H or W < window or the mask is all zero): callers need no memset.
+ *   The mask gets no gradient. The other argument errors are the forward's.
+ * oflow_charbonnier_loss_f32: on every pixel (no interior),
+ *     rho(p) = mean_c (((x - y) / image_range)^2 + eps^2)^alpha,  loss = sum mask rho / (sum mask + 1e-6).
+ *   x - y is formed in fp64 and rounded once; the rest is fp32 with IEEE division, sqrtf when alpha is 0.5 and powf
+ *   otherwise. eps, alpha and image_range are the fp32 values passed. d_workspace: oflow_ssim_loss_workspace_bytes(B, H,
+ *   W) bytes are enough (one row of 2 doubles per 1024 pixels, never more than one per tile). eps not positive and
+ *   finite, alpha outside (0, 1], image_range not positive and finite: OFLOW_E_SHAPE; the rest as the SSIM loss.
+ * oflow_charbonnier_loss_backward_f32: elementwise, with z = (x - y) / image_range and q = z^2 + eps^2,
+ *     dL/dx_c(p) = grad_loss * mask(p) / (sum mask + 1e-6) * (2 alpha / (C image_range)) * z * q^(alpha - 1)
+ *   and dL/dy_c(p) its negative. Outputs as for the SSIM backward.
+ */
+long long oflow_ssim_loss_workspace_bytes(int B, int H, int W);
+int oflow_ssim_loss_f32(const float* d_frame0, const float* d_frame1, const void* d_mask, int mask_kind, int B, int C,
+                        int H, int W, int window, const float* weights, float c1, float c2, float* d_ssim_map,
+                        double* d_workspace, float* d_loss, double* d_sum_m, void* stream);
+int oflow_ssim_loss_backward_f32(const float* d_grad_loss, const float* d_frame0, const float* d_frame1,
+                                 const void* d_mask, int mask_kind, const double* d_sum_m, int B, int C, int H, int W,
+                                 int window, const float* weights, float c1, float c2, float* d_grad_frame0,
+                                 float* d_grad_frame1, void* stream);
+int oflow_charbonnier_loss_f32(const float* d_frame0, const float* d_frame1, const void* d_mask, int mask_kind, int B,
+                               int C, int H, int W, float eps, float alpha, float image_range, double* d_workspace,
+                               float* d_loss, double* d_sum_m, void* stream);
+int oflow_charbonnier_loss_backward_f32(const float* d_grad_loss, const float* d_frame0, const float* d_frame1,
+                                        const void* d_mask, int mask_kind, const double* d_sum_m, int B, int C, int H,
+                                        int W, float eps, float alpha, float image_range, float* d_grad_frame0,
+                                        float* d_grad_frame1, void* stream);
 
 /*
  * Training-batch augmentation (csrc/augment.hip): the reference's FlowAugmentor / SparseFlowAugmentor

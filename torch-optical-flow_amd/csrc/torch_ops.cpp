@@ -49,6 +49,10 @@
 //   census_loss_backward(grad_loss, frame0, frame1, mask?, sum_m, s_map, patch, image_range, mask2) -> (grad_frame0, grad_frame1)
 //   smoothness_loss(flow, image, order, edge_weight, image_range) -> loss             edge-aware smoothness (smoothness_loss.hip)
 //   smoothness_loss_backward(grad_loss, flow, image, order, edge_weight, image_range) -> grad_flow
+//   ssim_loss(frame0, frame1, mask?, window, c1, c2, with_map) -> (loss, sum_m, ssim_map)   SSIM loss (photometric_loss.hip)
+//   ssim_loss_backward(grad_loss, frame0, frame1, mask?, sum_m, window, c1, c2, mask2) -> (grad_frame0, grad_frame1)
+//   charbonnier_loss(frame0, frame1, mask?, eps, alpha, image_range) -> (loss, sum_m)        robust L1 (photometric_loss.hip)
+//   charbonnier_loss_backward(grad_loss, frame0, frame1, mask?, sum_m, eps, alpha, image_range, mask2) -> (grad_frame0, grad_frame1)
 #include <array>
 #include <torch/library.h>
 #include <ATen/ATen.h>
@@ -1303,6 +1307,154 @@ Tensor smoothness_loss_backward(bool run, const Tensor& gloss, const Tensor& flo
   return gf;
 }
 
+// ---------------------------------------------------------------- photometric losses (photometric_loss.hip)
+// the checks the two losses share: the frames, the mask and the kernels' range
+void check_photometric(const Tensor& f0, const Tensor& f1, const c10::optional<Tensor>& mask, bool run, const char* what) {
+  if (run) {
+    check_on_gpu(f0, "frame0", what), check_on_gpu(f1, "frame1", what);
+    if (mask.has_value()) check_on_gpu(*mask, "mask", what);
+  }
+  TORCH_CHECK(f0.dim() == 4 && f0.sizes() == f1.sizes(), what, ": frame0 ", f0.sizes(), " and frame1 ", f1.sizes(),
+              " must be equal (B, C, H, W)");
+  TORCH_CHECK(f0.device() == f1.device(), what, ": frame0 and frame1 are on different devices");
+  const int64_t b = f0.size(0), h = f0.size(2), w = f0.size(3);
+  if (mask.has_value()) {
+    TORCH_CHECK(mask->dim() == 4 && mask->size(0) == b && mask->size(1) == 1 && mask->size(2) == h && mask->size(3) == w,
+                what, ": mask must be (B, 1, H, W) = (", b, ", 1, ", h, ", ", w, "), got ", mask->sizes());
+    TORCH_CHECK(mask->scalar_type() == at::kBool || mask->is_floating_point(), what, ": mask must be float or bool, got ",
+                mask->scalar_type());
+    TORCH_CHECK(mask->device() == f0.device(), what, ": frame0 and mask are on different devices");
+  }
+  TORCH_CHECK(b <= 65535 && f0.size(1) <= INT_MAX && h * w <= (int64_t(1) << 28), what, ": frames ", f0.sizes(),
+              " are past the kernels' range (B <= 65535, H*W <= 2^28)");
+}
+
+// the 1-D window as the C ABI takes it (fp32 in host memory)
+std::vector<float> check_ssim(at::ArrayRef<double> window, double c1, double c2, const char* what) {
+  const size_t n = window.size();
+  TORCH_CHECK(n == 3 || n == 5 || n == 7 || n == 9 || n == 11, what, ": a window of ", n,
+              " weights is not one of 3, 5, 7, 9, 11");
+  std::vector<float> w(n);
+  for (size_t i = 0; i < n; ++i) {
+    TORCH_CHECK(std::isfinite(window[i]), what, ": window weight ", i, " is not finite");
+    w[i] = (float)window[i];
+  }
+  TORCH_CHECK(c1 > 0 && c2 > 0 && std::isfinite(c1) && std::isfinite(c2), what, ": c1 ", c1, " and c2 ", c2,
+              " must be positive and finite");
+  return w;
+}
+
+// grad_loss and sum_m of a backward, as the kernels take them
+void check_loss_scalars(const Tensor& gloss, const Tensor& sum_m, const Tensor& frame0, bool run, const char* what) {
+  if (run) check_on_gpu(gloss, "grad_loss", what), check_on_gpu(sum_m, "sum_m", what);
+  TORCH_CHECK(gloss.numel() == 1 && sum_m.numel() == 1, what, ": grad_loss and sum_m must hold one element each");
+  TORCH_CHECK(gloss.device() == frame0.device() && sum_m.device() == frame0.device(), what,
+              ": all tensors must be on one device");
+}
+
+// (loss fp32 0-dim, sum M fp64 0-dim, mean_c SSIM (B, 1, H, W) fp32, empty without with_map); any float dtype or strides
+Tensor3 ssim_loss(bool run, const Tensor& frame0, const Tensor& frame1, const c10::optional<Tensor>& mask,
+                  at::ArrayRef<double> window, double c1, double c2, bool with_map) {
+  const char* what = "ssim_loss";
+  check_photometric(frame0, frame1, mask, run, what);
+  const std::vector<float> wt = check_ssim(window, c1, c2, what);
+  const int64_t b = frame0.size(0), c = frame0.size(1), h = frame0.size(2), w = frame0.size(3);
+  const auto opt = frame0.options().dtype(at::kFloat);
+  Tensor loss = at::empty({}, opt), sum_m = at::empty({}, opt.dtype(at::kDouble));
+  Tensor map = with_map ? at::empty({b, 1, h, w}, opt) : at::empty({0}, opt);
+  if (!run) return Tensor3(loss, sum_m, map);
+  if (frame0.numel() == 0) return Tensor3(loss.zero_(), sum_m.zero_(), map.zero_());
+  Tensor f0 = gpu_f32(frame0, "frame0", what), f1 = gpu_f32(frame1, "frame1", what), mk;
+  const void* mp;
+  const int kind = loss_mask(mask, mk, mp);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(f0.device());
+  Tensor ws = at::empty({oflow_ssim_loss_workspace_bytes((int)b, (int)h, (int)w) / 8}, opt.dtype(at::kDouble));
+  check_status(oflow_ssim_loss_f32(f0.data_ptr<float>(), f1.data_ptr<float>(), mp, kind, (int)b, (int)c, (int)h, (int)w,
+                                   (int)wt.size(), wt.data(), (float)c1, (float)c2,
+                                   with_map ? map.data_ptr<float>() : nullptr, ws.data_ptr<double>(),
+                                   loss.data_ptr<float>(), sum_m.data_ptr<double>(), cur_stream()),
+               what);
+  return Tensor3(loss, sum_m, map);
+}
+
+std::tuple<Tensor, Tensor> ssim_loss_backward(bool run, const Tensor& gloss, const Tensor& frame0, const Tensor& frame1,
+                                              const c10::optional<Tensor>& mask, const Tensor& sum_m,
+                                              at::ArrayRef<double> window, double c1, double c2, std::array<bool, 2> om) {
+  const char* what = "ssim_loss backward";
+  check_loss_scalars(gloss, sum_m, frame0, run, what);
+  check_photometric(frame0, frame1, mask, run, what);
+  const std::vector<float> wt = check_ssim(window, c1, c2, what);
+  const int64_t b = frame0.size(0), c = frame0.size(1), h = frame0.size(2), w = frame0.size(3);
+  const auto opt = frame0.options().dtype(at::kFloat);
+  Tensor g0 = wanted(om[0], {b, c, h, w}, opt), g1 = wanted(om[1], {b, c, h, w}, opt);
+  if (!run || !(om[0] || om[1]) || frame0.numel() == 0) return {g0, g1};
+  Tensor go = gpu_f32(gloss, "grad_loss", what), f0 = gpu_f32(frame0, "frame0", what), f1 = gpu_f32(frame1, "frame1", what);
+  Tensor sm = sum_m.to(at::kDouble).contiguous(), mk;
+  const void* mp;
+  const int kind = loss_mask(mask, mk, mp);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(f0.device());
+  check_status(oflow_ssim_loss_backward_f32(go.data_ptr<float>(), f0.data_ptr<float>(), f1.data_ptr<float>(), mp, kind,
+                                            sm.data_ptr<double>(), (int)b, (int)c, (int)h, (int)w, (int)wt.size(),
+                                            wt.data(), (float)c1, (float)c2, om[0] ? g0.data_ptr<float>() : nullptr,
+                                            om[1] ? g1.data_ptr<float>() : nullptr, cur_stream()),
+               what);
+  return {g0, g1};
+}
+
+void check_charbonnier(double eps, double alpha, double range, const char* what) {
+  TORCH_CHECK(eps > 0 && std::isfinite(eps), what, ": eps ", eps, " must be positive and finite");
+  TORCH_CHECK(alpha > 0 && alpha <= 1, what, ": alpha ", alpha, " must be in (0, 1]");
+  TORCH_CHECK(range > 0 && std::isfinite(range), what, ": image_range ", range, " must be positive and finite");
+}
+
+// (loss fp32 0-dim, sum of the mask fp64 0-dim)
+std::tuple<Tensor, Tensor> charbonnier_loss(bool run, const Tensor& frame0, const Tensor& frame1,
+                                            const c10::optional<Tensor>& mask, double eps, double alpha, double range) {
+  const char* what = "charbonnier_loss";
+  check_photometric(frame0, frame1, mask, run, what);
+  check_charbonnier(eps, alpha, range, what);
+  const int64_t b = frame0.size(0), c = frame0.size(1), h = frame0.size(2), w = frame0.size(3);
+  const auto opt = frame0.options().dtype(at::kFloat);
+  Tensor loss = at::empty({}, opt), sum_m = at::empty({}, opt.dtype(at::kDouble));
+  if (!run) return {loss, sum_m};
+  if (frame0.numel() == 0) return {loss.zero_(), sum_m.zero_()};
+  Tensor f0 = gpu_f32(frame0, "frame0", what), f1 = gpu_f32(frame1, "frame1", what), mk;
+  const void* mp;
+  const int kind = loss_mask(mask, mk, mp);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(f0.device());
+  Tensor ws = at::empty({oflow_ssim_loss_workspace_bytes((int)b, (int)h, (int)w) / 8}, opt.dtype(at::kDouble));
+  check_status(oflow_charbonnier_loss_f32(f0.data_ptr<float>(), f1.data_ptr<float>(), mp, kind, (int)b, (int)c, (int)h,
+                                          (int)w, (float)eps, (float)alpha, (float)range, ws.data_ptr<double>(),
+                                          loss.data_ptr<float>(), sum_m.data_ptr<double>(), cur_stream()),
+               what);
+  return {loss, sum_m};
+}
+
+std::tuple<Tensor, Tensor> charbonnier_loss_backward(bool run, const Tensor& gloss, const Tensor& frame0,
+                                                     const Tensor& frame1, const c10::optional<Tensor>& mask,
+                                                     const Tensor& sum_m, double eps, double alpha, double range,
+                                                     std::array<bool, 2> om) {
+  const char* what = "charbonnier_loss backward";
+  check_loss_scalars(gloss, sum_m, frame0, run, what);
+  check_photometric(frame0, frame1, mask, run, what);
+  check_charbonnier(eps, alpha, range, what);
+  const int64_t b = frame0.size(0), c = frame0.size(1), h = frame0.size(2), w = frame0.size(3);
+  const auto opt = frame0.options().dtype(at::kFloat);
+  Tensor g0 = wanted(om[0], {b, c, h, w}, opt), g1 = wanted(om[1], {b, c, h, w}, opt);
+  if (!run || !(om[0] || om[1]) || frame0.numel() == 0) return {g0, g1};
+  Tensor go = gpu_f32(gloss, "grad_loss", what), f0 = gpu_f32(frame0, "frame0", what), f1 = gpu_f32(frame1, "frame1", what);
+  Tensor sm = sum_m.to(at::kDouble).contiguous(), mk;
+  const void* mp;
+  const int kind = loss_mask(mask, mk, mp);
+  c10::hip::HIPGuardMasqueradingAsCUDA g(f0.device());
+  check_status(oflow_charbonnier_loss_backward_f32(go.data_ptr<float>(), f0.data_ptr<float>(), f1.data_ptr<float>(), mp,
+                                                   kind, sm.data_ptr<double>(), (int)b, (int)c, (int)h, (int)w, (float)eps,
+                                                   (float)alpha, (float)range, om[0] ? g0.data_ptr<float>() : nullptr,
+                                                   om[1] ? g1.data_ptr<float>() : nullptr, cur_stream()),
+               what);
+  return {g0, g1};
+}
+
 // ---------------------------------------------------------------- training-batch augmentation (augment.hip)
 Tensor4 augment_batch(bool run, const Tensor& img1, const Tensor& img2, const Tensor& flow,
                       const c10::optional<Tensor>& valid, const Tensor& params, int64_t ch, int64_t cw) {
@@ -1426,6 +1578,10 @@ TORCH_LIBRARY(oflow, m) {
   m.def("census_loss_backward(Tensor grad_loss, Tensor frame0, Tensor frame1, Tensor? mask, Tensor sum_m, Tensor s_map, int patch, float image_range, bool[2] output_mask) -> (Tensor, Tensor)");
   m.def("smoothness_loss(Tensor flow, Tensor image, int order, float edge_weight, float image_range) -> Tensor");
   m.def("smoothness_loss_backward(Tensor grad_loss, Tensor flow, Tensor image, int order, float edge_weight, float image_range) -> Tensor");
+  m.def("ssim_loss(Tensor frame0, Tensor frame1, Tensor? mask, float[] window, float c1, float c2, bool with_map) -> (Tensor loss, Tensor sum_m, Tensor ssim_map)");
+  m.def("ssim_loss_backward(Tensor grad_loss, Tensor frame0, Tensor frame1, Tensor? mask, Tensor sum_m, float[] window, float c1, float c2, bool[2] output_mask) -> (Tensor, Tensor)");
+  m.def("charbonnier_loss(Tensor frame0, Tensor frame1, Tensor? mask, float eps, float alpha, float image_range) -> (Tensor loss, Tensor sum_m)");
+  m.def("charbonnier_loss_backward(Tensor grad_loss, Tensor frame0, Tensor frame1, Tensor? mask, Tensor sum_m, float eps, float alpha, float image_range, bool[2] output_mask) -> (Tensor, Tensor)");
 
   bind<&corr_pyramid>(m, "corr_pyramid");
   bind<&corr_pyramid_tiled>(m, "corr_pyramid_tiled");
@@ -1466,4 +1622,8 @@ TORCH_LIBRARY(oflow, m) {
   bind<&census_loss_backward>(m, "census_loss_backward");
   bind<&smoothness_loss>(m, "smoothness_loss");
   bind<&smoothness_loss_backward>(m, "smoothness_loss_backward");
+  bind<&ssim_loss>(m, "ssim_loss");
+  bind<&ssim_loss_backward>(m, "ssim_loss_backward");
+  bind<&charbonnier_loss>(m, "charbonnier_loss");
+  bind<&charbonnier_loss_backward>(m, "charbonnier_loss_backward");
 }

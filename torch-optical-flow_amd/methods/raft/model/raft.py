@@ -217,21 +217,25 @@ class RAFT(nn.Module):
         return loss
 
     def unsupervised_step(self, batch: Tuple[Tensor, Tensor], batch_idx: int = 0, w_census: float = 1.0,
-                          w_smooth: float = 1.0, smooth_order: int = 1) -> Tensor:
+                          w_smooth: float = 1.0, smooth_order: int = 1, w_ssim: float = 0.0,
+                          w_charbonnier: float = 0.0, ssim_window: int = 3, ssim_sigma: Optional[float] = None) -> Tensor:
         """One training batch ``(img0, img1)`` without ground truth (an addition; the reference has none): both flow
         directions from ``forward_bidirectional`` with ``hparams.iters`` refinements, the occlusion masks of the last
         predictions under ``no_grad`` (``optical_flow.fb_consistency(..., both=True)``), and
         ``unsupervised_sequence_loss`` with ``hparams.gamma`` summed over both directions with ``mask = ~occluded``.
         Returns the loss for the caller's ``backward()``; like ``training_step`` it does no logging and has no
         optimizer, and nothing in it synchronises with the host. The weights are plain keyword defaults and untuned:
-        the papers this follows (UnFlow, UFlow) weigh the smoothness term per dataset."""
+        the papers this follows (UnFlow, UFlow) weigh the smoothness term per dataset. ``w_ssim`` and
+        ``w_charbonnier`` switch on the two other photometric terms (``unsupervised_sequence_loss``); at 0, the default,
+        they are not evaluated at all."""
         from optical_flow import fb_consistency
 
         img0, img1 = batch
         preds_fw, preds_bw = self.forward_bidirectional(img0, img1, iters=self.hparams.iters)
         with torch.no_grad():
             occ_fw, occ_bw = fb_consistency(preds_fw[-1], preds_bw[-1], both=True)
-        kw = dict(gamma=self.hparams.gamma, w_census=w_census, w_smooth=w_smooth, smooth_order=smooth_order)
+        kw = dict(gamma=self.hparams.gamma, w_census=w_census, w_smooth=w_smooth, smooth_order=smooth_order,
+                  w_ssim=w_ssim, w_charbonnier=w_charbonnier, ssim_window=ssim_window, ssim_sigma=ssim_sigma)
         return (unsupervised_sequence_loss(preds_fw, img0, img1, mask=~occ_fw, **kw)
                 + unsupervised_sequence_loss(preds_bw, img1, img0, mask=~occ_bw, **kw))
 
@@ -665,6 +669,10 @@ def unsupervised_sequence_loss(
     w_census: float = 1.0,
     w_smooth: float = 1.0,
     smooth_order: int = 1,
+    w_ssim: float = 0.0,
+    w_charbonnier: float = 0.0,
+    ssim_window: int = 3,
+    ssim_sigma: Optional[float] = None,
 ) -> Tensor:
     """``sequence_loss`` without ground truth (an addition; the reference has none): every prediction is scored against
     the images alone,
@@ -676,8 +684,13 @@ def unsupervised_sequence_loss(
     differentiable ``optical_flow.warp``. ``mask`` (B, 1, H, W), float or bool, is the census term's: in the intended
     use ``~occluded`` from ``optical_flow.fb_consistency``. ``align_corners=True`` is deliberate: it is the convention
     ``normalize`` uses, and with ``False`` ``warp`` is not the identity at zero flow (quirk Q8 in
-    optical_flow/operator/operator.py). The weights are plain defaults, untuned. Images in [0, 255]."""
-    from optical_flow import census_loss, normalize, smoothness_loss, warp, warp_grid
+    optical_flow/operator/operator.py). The weights are plain defaults, untuned. Images in [0, 255].
+
+    ``w_ssim`` and ``w_charbonnier`` add ``w_ssim * ssim_loss(image0, warped, mask, window=ssim_window,
+    sigma=ssim_sigma) + w_charbonnier * charbonnier_loss(image0, warped, mask)`` to each prediction's term, on the same
+    warped image and the same mask as the census term (ARFlow's mix is L1 + SSIM + ternary). A weight of exactly 0, the
+    default, skips its term entirely -- no kernel, no graph node -- so the defaults give the value they always gave."""
+    from optical_flow import census_loss, charbonnier_loss, normalize, smoothness_loss, ssim_loss, warp, warp_grid
 
     n = len(flow_preds)
     loss = 0.0
@@ -688,5 +701,9 @@ def unsupervised_sequence_loss(
             grid = warp_grid(normalize(flow).permute(0, 2, 3, 1))
             warped = F.grid_sample(image1, grid.to(image1.dtype), mode="bilinear", padding_mode="border", align_corners=True)
         term = w_census * census_loss(image0, warped, mask) + w_smooth * smoothness_loss(flow, image0, order=smooth_order)
+        if w_ssim != 0:
+            term = term + w_ssim * ssim_loss(image0, warped, mask, window=ssim_window, sigma=ssim_sigma)
+        if w_charbonnier != 0:
+            term = term + w_charbonnier * charbonnier_loss(image0, warped, mask)
         loss = loss + gamma ** (n - 1 - i) * term
     return loss

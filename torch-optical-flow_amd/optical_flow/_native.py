@@ -137,6 +137,11 @@ def _signatures():
         "oflow_smoothness_loss_workspace_bytes": (L, [I, I, I]),
         "oflow_smoothness_loss_f32": (I, [P, P, I, I, I, I, I, F, F, P, P, P]),
         "oflow_smoothness_loss_backward_f32": (I, [P, P, P, I, I, I, I, I, F, F, P, P]),
+        "oflow_ssim_loss_workspace_bytes": (L, [I, I, I]),
+        "oflow_ssim_loss_f32": (I, [P, P, P, I, I, I, I, I, I, FP, F, F, P, P, P, P, P]),
+        "oflow_ssim_loss_backward_f32": (I, [P, P, P, P, I, P, I, I, I, I, I, FP, F, F, P, P, P]),
+        "oflow_charbonnier_loss_f32": (I, [P, P, P, I, I, I, I, I, F, F, F, P, P, P, P]),
+        "oflow_charbonnier_loss_backward_f32": (I, [P, P, P, P, I, P, I, I, I, I, F, F, F, P, P, P]),
     }
 
 
@@ -520,6 +525,30 @@ def smoothness_loss(flow: torch.Tensor, image: torch.Tensor, order: int, edge_we
     fl, im = _tensor(flow, "flow", what), _tensor(image, "image", what)
     return _run(what, fl.device, ops().smoothness_loss, fl, im.detach(), int(order), float(edge_weight),
                 float(image_range))
+
+
+def ssim_loss(frame0: torch.Tensor, frame1: torch.Tensor, mask: Optional[torch.Tensor], weights: Sequence[float],
+              c1: float, c2: float, with_map: bool):
+    """The SSIM loss of two (B, C, H, W) frames under the separable window of the 1-D ``weights``
+    (``torch.ops.oflow.ssim_loss``, include/oflow.h oflow_ssim_loss_f32): (loss fp32 0-dim, sum M fp64 0-dim, mean_c SSIM
+    (B, 1, H, W) fp32, empty unless ``with_map``), bit-reproducible. Differentiable in the two frames (native gather,
+    csrc/photometric_loss.hip); sum M and the map are not."""
+    what = "ssim_loss"
+    f0, f1 = _tensor(frame0, "frame0", what), _tensor(frame1, "frame1", what)
+    me = None if mask is None else _tensor(mask, "mask", what)
+    return _run(what, f0.device, ops().ssim_loss, f0, f1, me, [float(w) for w in weights], float(c1), float(c2),
+                bool(with_map))
+
+
+def charbonnier_loss(frame0: torch.Tensor, frame1: torch.Tensor, mask: Optional[torch.Tensor], eps: float, alpha: float,
+                     image_range: float):
+    """The Charbonnier loss of two (B, C, H, W) frames (``torch.ops.oflow.charbonnier_loss``, include/oflow.h
+    oflow_charbonnier_loss_f32): (loss fp32 0-dim, sum of the mask fp64 0-dim), bit-reproducible. Differentiable in the
+    two frames (csrc/photometric_loss.hip); the sum is not."""
+    what = "charbonnier_loss"
+    f0, f1 = _tensor(frame0, "frame0", what), _tensor(frame1, "frame1", what)
+    me = None if mask is None else _tensor(mask, "mask", what)
+    return _run(what, f0.device, ops().charbonnier_loss, f0, f1, me, float(eps), float(alpha), float(image_range))
 
 
 def augment_batch(img1: torch.Tensor, img2: torch.Tensor, flow: torch.Tensor, valid: Optional[torch.Tensor],

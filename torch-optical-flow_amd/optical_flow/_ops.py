@@ -70,6 +70,12 @@ in the flows and has no gradient, and the residual is returned for inspection an
     csrc/smoothness_loss.hip) gathers each flow pixel's two or three differences per direction, and the image, which
     is data, gets none. No atomics and fixed-order fp64 sums in both directions: bit-reproducible. The four ops are
     listed in ``OPS_LOSSES``, not in ``OPS`` or ``OPS_SPLAT``.
+  * ``ssim_loss`` / ``charbonnier_loss`` (``optical_flow.losses``, the other photometric terms): the forwards
+    (csrc/photometric_loss.hip) return (loss, sum M[, mean_c SSIM map]); the frames, the mask and sum M are saved, sum M
+    and the map are not differentiable, and the backwards (``ssim_loss_backward``, a tiled gather that recomputes the
+    window statistics from the frames; ``charbonnier_loss_backward``, elementwise) form only the frame gradients
+    ``needs_input_grad`` asks for; the mask gets none. No atomics and fixed-order fp64 sums: bit-reproducible. The four
+    ops are listed in ``OPS_PHOTOMETRIC``.
 """
 from __future__ import annotations
 
@@ -128,6 +134,14 @@ OPS_LOSSES = (
     "census_loss_backward",
     "smoothness_loss",
     "smoothness_loss_backward",
+)
+# the SSIM and Charbonnier losses, kept apart likewise (tests/test_losses_host.py records OPS_LOSSES as it stood); their
+# schemas are recorded in tests/golden/op_schemas_photometric.txt
+OPS_PHOTOMETRIC = (
+    "ssim_loss",
+    "ssim_loss_backward",
+    "charbonnier_loss",
+    "charbonnier_loss_backward",
 )
 _loaded = False
 
@@ -345,6 +359,31 @@ def _smoothness_backward(ctx, grad_loss):
     return g.to(flow.dtype), None, None, None, None
 
 
+def _photometric_formula(backward_op, n_outputs):
+    """(setup_context, backward) of ``ssim_loss`` and ``charbonnier_loss``: inputs (frame0, frame1, mask, plain
+    arguments...), outputs (loss, sum M, ...), backward op (grad_loss, frame0, frame1, mask, sum M, plain arguments...,
+    output_mask) -> (grad_frame0, grad_frame1). ``ssim_loss``'s last plain argument, ``with_map``, is not the
+    backward's."""
+    n_plain = 3
+
+    def setup(ctx, inputs, output):
+        frame0, frame1, mask = inputs[:3]
+        ctx.save_for_backward(frame0, frame1, mask, output[1])
+        ctx.args = tuple(inputs[3:3 + n_plain])
+        ctx.n_inputs = len(inputs)
+        ctx.mark_non_differentiable(*output[1:])
+
+    def backward(ctx, grad_loss, *_grads):
+        frame0, frame1, mask, sum_m = ctx.saved_tensors
+        need = [bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])]
+        g0, g1 = backward_op(grad_loss.contiguous(), frame0, frame1, mask, sum_m, *ctx.args, need)
+        return ((g0.to(frame0.dtype) if need[0] else None), (g1.to(frame1.dtype) if need[1] else None)) + \
+            (None,) * (ctx.n_inputs - 2)
+
+    assert n_outputs in (2, 3)
+    return setup, backward
+
+
 def _register_autograd() -> None:
     ops = torch.ops.oflow
 
@@ -367,3 +406,5 @@ def _register_autograd() -> None:
     reg("oflow::splat", _splat_setup, _splat_backward)
     reg("oflow::census_loss", _census_setup, _census_backward)
     reg("oflow::smoothness_loss", _smoothness_setup, _smoothness_backward)
+    reg("oflow::ssim_loss", *_photometric_formula(ops.ssim_loss_backward, n_outputs=3))
+    reg("oflow::charbonnier_loss", *_photometric_formula(ops.charbonnier_loss_backward, n_outputs=2))
